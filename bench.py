@@ -6,17 +6,22 @@ One step = GaussianProcess.fit_gp(x, y) + GaussianProcess.mean_std(xtest) on syn
 shape (x ~ U(-1,1)^{N x d}, y = sin(sum x) + 0.1 N(0,1), M = 4096 test points,
 SE kernel gamma = sqrt(d), s = 0.1, kappa = 1, fp64), inputs resident in HBM before the timed region.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (block-cyclic path)
 
-Rank 0 prints ONE JSON line.  `value` = seconds per step (max over ranks), lower is better.
+Rank 0 prints ONE JSON line.  `value` = seconds per step (max over ranks), lower is better; `ms_per_step` = the same in ms.
+A plain run sets up, warms up, times exactly --steps steps and prints that line, nothing else.  --dump-outputs DIR writes
+what the last timed step returned (mean_std's mu and std, float64) as DIR/<name>.npy; the inputs are seeded, so two builds
+run with the same arguments can be compared output for output.
+--full adds everything else below (off by default):
 `roofline` is for the dominant kernel family, the fp64-MFMA contraction gemm_nt_dtv_kernel<double,SUB> (+ the sliver / K = 128 /
 tile forms of the panel chain) under potrf and trsm: achieved = sum of the algorithmic flops of its launches / the length of
 the UNION of their intervals (look-ahead launches overlap the trailing update), measured live with HIP events recorded on the
 launch stream inside libstpy_hip (stpy_profile_*); tools/trace_union.py derives the same figure from a rocprofv3 kernel trace
 (profiles/r02_*_union.json).  `extra_configs` holds BASELINE configs 2, 3 and 5 with their own roofline fraction and parity.
 `cpu_baseline` times the CPU oracle (numpy/LAPACK restatement, kind "port") on a bounded sample, checks the HIP path against
-it, and adds the reference-shaped op sequence over an N sweep with a power-law extrapolation.
+it, and adds the reference-shaped op sequence over an N sweep with a power-law extrapolation.  Multi-GPU runs check the
+distributed path against the single-GPU class before timing and report per-rank traffic (`multi_gpu`).
 """
 import argparse
 import ctypes
@@ -419,6 +424,11 @@ def parse_args(argv=None):
 	ap.add_argument("--nb-dist", type=int, default=0, help="distribution block of the block-cyclic path (0: the class default for the size)")
 	ap.add_argument("--transport", choices=["collective", "fanout", "auto"], default=os.environ.get("STPY_DIST_TRANSPORT", "collective"),
 					help="panel broadcasts of the block-cyclic path: RCCL broadcast (default) or point-to-point fan-out to every peer")
+	ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+					help="write the last timed step's outputs (mu, std of mean_std; float64) as DIR/<name>.npy")
+	ap.add_argument("--full", action="store_true",
+					help="also measure and check everything beyond the headline: live roofline, multi-GPU self-check, the C4 shape, "
+						 "the other BASELINE configs and the CPU baseline (the two --no-* options below trim a --full run)")
 	ap.add_argument("--no-cpu-baseline", action="store_true")
 	ap.add_argument("--cpu-baseline-long", action="store_true", help="extend the reference-shaped CPU sweep to N = 8192 (about a minute more of host time)")
 	ap.add_argument("--no-extra-configs", action="store_true")
@@ -523,6 +533,24 @@ def max_over_ranks(elapsed, world, backend, dev):
 	return elapsed
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+	"""arrays: name -> device tensor with one row per test point.  Written as float64 .npy; above DUMP_LIMIT_BYTES in all, the
+	same fixed, seeded sample of rows is taken from every array."""
+	os.makedirs(out_dir, exist_ok=True)
+	host = {k: v.detach().to(torch.float64).cpu().numpy() for k, v in arrays.items()}
+	total = sum(a.nbytes for a in host.values())
+	if total > DUMP_LIMIT_BYTES:
+		rows = next(iter(host.values())).shape[0]
+		keep = int(rows * DUMP_LIMIT_BYTES // total)
+		idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+		host = {k: a[idx] for k, a in host.items()}
+	for k, a in host.items():
+		np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def traffic_from_profiles(lib_version, launches_per_step):
 	"""HBM traffic of the dominant kernel family: PMC counters cannot be collected inside this process, so the value comes from
 	the committed separate-pass rocprofv3 --pmc runs of this same command (profiles/*_pmc_traffic.json: FETCH_SIZE doubled per the
@@ -553,6 +581,55 @@ def traffic_from_profiles(lib_version, launches_per_step):
 	info["traffic"] = round(rec["per_launch_hbm_bytes"])
 	info["traffic_note"] = "HBM bytes per launch of this kernel family from separate rocprofv3 --pmc passes of this command with this build, 2*FETCH_SIZE + WRITE_SIZE"
 	return info
+
+
+def headline_extras(args, lib, lib_version, gp, mu, std, selfcheck, dist_path, world, rank, backend):
+	"""--full: what the timed steps recorded beyond their time (the live roofline from the library's event log, per-rank traffic
+	of the distributed path, a result check); every rank calls it (one all-gather on the distributed path)."""
+	from stpy_amd import _lib
+	n, d, m = args.n, args.d, args.m
+	# ---- live roofline of the dominant kernel from the event log (this rank)
+	def prof(tag):
+		ms, fl, cnt = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int64(0)
+		_lib.check(lib.stpy_profile_read(tag, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(cnt)), "stpy_profile_read")
+		return ms.value, fl.value, cnt.value
+	tags = {"syrk": 0, "panel_gemm": 1, "trsm_gemm": 2, "potf2": 3, "gemm_api": 4}
+	pr = {k: prof(v) for k, v in tags.items()}
+	# the block-cyclic path issues its trailing updates through stpy_gemm_nt_bc (tag 4)
+	gemm_tags = ["syrk", "panel_gemm", "trsm_gemm"] + (["gemm_api"] if dist_path else [])
+	g_ms = sum(pr[t][0] for t in gemm_tags)
+	g_fl = sum(pr[t][1] for t in gemm_tags)
+	g_cnt = sum(pr[t][2] for t in gemm_tags)
+	# launches on the look-ahead stream overlap the trailing update: time them as the union of intervals
+	ub, uf, uc = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int64(0)
+	_lib.check(lib.stpy_profile_read_union(0b10111 if dist_path else 0b0111, ctypes.byref(ub), ctypes.byref(uf), ctypes.byref(uc)), "stpy_profile_read_union")
+	achieved = uf.value / (ub.value * 1e-3) / 1e12 if ub.value > 0 else 0.0
+
+	tinfo = {"traffic": None, "traffic_source": None, "traffic_note": "null: only recorded for the single-GPU headline workload"}
+	if (n, d, m) == WORKLOADS["headline"] and not dist_path:
+		tinfo = traffic_from_profiles(lib_version, g_cnt / max(args.steps, 1))
+
+	# ---- multi-GPU: what moved and how busy every rank's MFMA GEMM was (gathered; one small host object per rank)
+	dist_info = None
+	if dist_path:
+		mine = {"rank": rank, "gemm_busy_ms_per_step": round(ub.value / args.steps, 2),
+				"bcast_MB_per_step": round(gp.stats["bcast_bytes"] / 1e6 / (args.steps + args.warmup), 1),
+				"reduce_MB_per_step": round(gp.stats["reduce_bytes"] / 1e6 / (args.steps + args.warmup), 1),
+				"collectives_per_step": gp.stats["collectives"] // max(args.steps + args.warmup, 1)}
+		gathered = [None] * world
+		torch.distributed.all_gather_object(gathered, mine)
+		dist_info = {"rccl_ranks": world if backend == "nccl" else 0, "backend": backend, "grid": "%dx%d" % (gp.Pr, gp.Pc), "nb_dist": gp.NB,
+					 "transport": getattr(gp, "transport", "collective"), "col_exchange": getattr(gp, "col_exchange", None), "selfcheck": selfcheck, "per_rank": gathered}
+	result_check = {"mu_norm": float(torch.norm(mu)), "std_mean": float(std.mean()), "nan": bool(torch.isnan(std).any())}
+	out = {"roofline": dict({"bound": "mfma", "kernel": "stpy::gemm_nt_dtv_kernel / gemm_nt_kernel<double>" if dist_path else "stpy::gemm_nt_dtv_kernel<SUB> (+ gemm_nt_kernel<double,...> for the ragged / fused-epilogue launches)", "achieved": round(achieved, 2), "peak": PEAK_FP64_MFMA_TFLOPS,
+							  "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP64_MFMA_TFLOPS, 4)}, **tinfo,
+							  **{"launches": int(g_cnt), "avg_launch_ms": round(g_ms / max(g_cnt, 1), 4), "busy_ms_per_step": round(ub.value / args.steps, 2),
+							  "algorithmic_gflop_per_launch": round(g_fl / max(g_cnt, 1) / 1e9, 3)}),
+		   "breakdown_ms_per_step": {k: round(v[0] / args.steps, 2) for k, v in pr.items()},
+		   "result_check": result_check}
+	if dist_info is not None:
+		out["multi_gpu"] = dist_info
+	return out
 
 
 def main(args):
@@ -607,10 +684,10 @@ def main(args):
 		g.nb = args.nb
 		return g
 
-	# Multi-GPU: before anything is timed, the distributed path is checked on a small problem against the single-GPU class on this
+	# --full, multi-GPU: before anything is timed, the distributed path is checked on a small problem against the single-GPU class on this
 	# very GPU (every rank holds the replicated result; a wrong collective order or a stale panel shows up here, not as a fast wrong number)
 	selfcheck = None
-	if dist_path:
+	if dist_path and args.full:
 		ns, ms = 4096 + 384, 256
 		xs, ys, xts = synth(ns, d, ms, dev, seed=99)
 		g1 = GaussianProcess(gamma=math.sqrt(d), s=s, kappa=1.0, kernel_name="squared_exponential", d=d)
@@ -633,43 +710,13 @@ def main(args):
 
 	x, y, xt = synth(n, d, m, dev)
 	gp = make_gp(d, n)
-	elapsed, (mu, std) = run_steps(gp, x, y, xt, args.warmup, args.steps, dist_path, lib)
+	elapsed, (mu, std) = run_steps(gp, x, y, xt, args.warmup, args.steps, dist_path, lib if args.full else None)
 	sec_per_step = max_over_ranks(elapsed, world, backend, dev) / args.steps
 
-	# ---- live roofline of the dominant kernel from the event log (this rank)
-	def prof(tag):
-		ms, fl, cnt = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int64(0)
-		_lib.check(lib.stpy_profile_read(tag, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(cnt)), "stpy_profile_read")
-		return ms.value, fl.value, cnt.value
-	tags = {"syrk": 0, "panel_gemm": 1, "trsm_gemm": 2, "potf2": 3, "gemm_api": 4}
-	pr = {k: prof(v) for k, v in tags.items()}
-	# the block-cyclic path issues its trailing updates through stpy_gemm_nt_bc (tag 4)
-	gemm_tags = ["syrk", "panel_gemm", "trsm_gemm"] + (["gemm_api"] if dist_path else [])
-	g_ms = sum(pr[t][0] for t in gemm_tags)
-	g_fl = sum(pr[t][1] for t in gemm_tags)
-	g_cnt = sum(pr[t][2] for t in gemm_tags)
-	# launches on the look-ahead stream overlap the trailing update: time them as the union of intervals
-	ub, uf, uc = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int64(0)
-	_lib.check(lib.stpy_profile_read_union(0b10111 if dist_path else 0b0111, ctypes.byref(ub), ctypes.byref(uf), ctypes.byref(uc)), "stpy_profile_read_union")
-	achieved = uf.value / (ub.value * 1e-3) / 1e12 if ub.value > 0 else 0.0
-
-	tinfo = {"traffic": None, "traffic_source": None, "traffic_note": "null: only recorded for the single-GPU headline workload"}
-	if (n, d, m) == WORKLOADS["headline"] and not dist_path:
-		tinfo = traffic_from_profiles(lib_version, g_cnt / max(args.steps, 1))
-
-	# ---- multi-GPU: what moved and how busy every rank's MFMA GEMM was (gathered; one small host object per rank)
-	dist_info = None
-	if dist_path:
-		mine = {"rank": rank, "gemm_busy_ms_per_step": round(ub.value / args.steps, 2),
-				"bcast_MB_per_step": round(gp.stats["bcast_bytes"] / 1e6 / (args.steps + args.warmup), 1),
-				"reduce_MB_per_step": round(gp.stats["reduce_bytes"] / 1e6 / (args.steps + args.warmup), 1),
-				"collectives_per_step": gp.stats["collectives"] // max(args.steps + args.warmup, 1)}
-		gathered = [None] * world
-		torch.distributed.all_gather_object(gathered, mine)
-		dist_info = {"rccl_ranks": world if backend == "nccl" else 0, "backend": backend, "grid": "%dx%d" % (gp.Pr, gp.Pc), "nb_dist": gp.NB,
-					 "transport": getattr(gp, "transport", "collective"), "col_exchange": getattr(gp, "col_exchange", None), "selfcheck": selfcheck, "per_rank": gathered}
+	if args.dump_outputs and rank == 0:
+		dump_outputs(args.dump_outputs, {"mu": mu, "std": std})
 	gp_nb = gp.NB if dist_path else None
-	result_check = {"mu_norm": float(torch.norm(mu)), "std_mean": float(std.mean()), "nan": bool(torch.isnan(std).any())}
+	extras = headline_extras(args, lib, lib_version, gp, mu, std, selfcheck, dist_path, world, rank, backend) if args.full else {}
 	del gp, mu, std, x, y, xt
 	torch.cuda.empty_cache()
 
@@ -688,15 +735,8 @@ def main(args):
 			"step_tflops": round(F / sec_per_step / 1e12, 2),
 			"step_frac_of_fp64_mfma_peak": round(F / sec_per_step / 1e12 / (PEAK_FP64_MFMA_TFLOPS * world), 4),
 			"library": lib_version,
-			"roofline": dict({"bound": "mfma", "kernel": "stpy::gemm_nt_dtv_kernel / gemm_nt_kernel<double>" if dist_path else "stpy::gemm_nt_dtv_kernel<SUB> (+ gemm_nt_kernel<double,...> for the ragged / fused-epilogue launches)", "achieved": round(achieved, 2), "peak": PEAK_FP64_MFMA_TFLOPS,
-						 "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP64_MFMA_TFLOPS, 4)}, **tinfo,
-						 **{"launches": int(g_cnt), "avg_launch_ms": round(g_ms / max(g_cnt, 1), 4), "busy_ms_per_step": round(ub.value / args.steps, 2),
-						 "algorithmic_gflop_per_launch": round(g_fl / max(g_cnt, 1) / 1e9, 3)}),
-			"breakdown_ms_per_step": {k: round(v[0] / args.steps, 2) for k, v in pr.items()},
-			"result_check": result_check,
 		}
-		if dist_info is not None:
-			out["multi_gpu"] = dist_info
+		out.update(extras)
 		if world > 1:
 			# the measured headline must survive whatever the extra workload below does to the process group (a rank that dies inside
 			# a collective takes the others down with the watchdog): it is put on stderr now, where bench.py's own launcher -- and
@@ -707,7 +747,7 @@ def main(args):
 	# ---- BASELINE config 4's shape (N = 131 072, d = 32): the strong-scaling target of north_star.  One GPU: the reference time
 	# ---- of the curve; several: seconds, speed-up over one GPU and the fraction of the aggregate fp64 MFMA peak.
 	c4 = None
-	if args.config == "headline" and not args.no_extra_configs and (n, d, m) == WORKLOADS["headline"] and os.environ.get("STPY_BENCH_SKIP_C4", "0") != "1":
+	if args.full and args.config == "headline" and not args.no_extra_configs and (n, d, m) == WORKLOADS["headline"] and os.environ.get("STPY_BENCH_SKIP_C4", "0") != "1":
 		n4, d4, m4 = WORKLOADS["c4"]
 		x4 = y4 = xt4 = g4 = None
 		ok, why = 1, ""
@@ -748,11 +788,11 @@ def main(args):
 		extra = {}
 		if c4 is not None:
 			extra["C4"] = c4
-		if world == 1 and not args.no_extra_configs and not dist_path:
+		if args.full and world == 1 and not args.no_extra_configs and not dist_path:
 			extra.update(extra_configs(dev, lib))
 		if extra:
 			out["extra_configs"] = extra
-		if world == 1 and not args.no_cpu_baseline and not dist_path:
+		if args.full and world == 1 and not args.no_cpu_baseline and not dist_path:
 			out["cpu_baseline"] = cpu_baseline(d, lambda: GaussianProcess(gamma=math.sqrt(d), s=s, kappa=1.0, kernel_name="squared_exponential", d=d), dev,
 											   long_sweep=args.cpu_baseline_long)
 		print(json.dumps(out), flush=True)

@@ -185,6 +185,24 @@ def test_bench_always_prints_one_json_line():
 		assert r.returncode != 0 and out["value"] is None and out["n_gpus"] == 8 and out["error"]
 
 
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path, monkeypatch):
+	"""bench.py --dump-outputs: outputs under the size limit are written whole as float64; above it every array keeps the same
+	seeded sample of rows, identical from run to run, and the files stay under the limit."""
+	import numpy as np
+	import torch
+	import bench
+	mu = torch.arange(4096, dtype=torch.float32).reshape(-1, 1)
+	bench.dump_outputs(str(tmp_path / "whole"), {"mu": mu, "std": -mu})
+	got = np.load(tmp_path / "whole" / "mu.npy")
+	assert got.dtype == np.float64 and np.array_equal(got, mu.double().numpy())
+	monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8192)
+	for run in ("a", "b"):
+		bench.dump_outputs(str(tmp_path / run), {"mu": mu, "std": -mu})
+	a_mu, a_std, b_mu = (np.load(tmp_path / r / (k + ".npy")) for r, k in (("a", "mu"), ("a", "std"), ("b", "mu")))
+	assert 0 < a_mu.shape[0] < 4096 and a_mu.nbytes + a_std.nbytes <= 8192
+	assert np.array_equal(a_mu, -a_std) and np.array_equal(a_mu, b_mu) and np.all(np.diff(a_mu[:, 0]) > 0)
+
+
 def test_round3_kernels_keep_their_occupancy(tmp_path):
 	"""gemm_nt_bf3_kernel (fp32 on the bf16 matrix cores): two workgroups per CU -- <= 256 VGPRs with BOTH accumulator sets (the
 	two-level accumulation) in registers, no scratch, 48 KiB of LDS.  gram_fill_f64_kernel: the squared-exponential and linear forms

@@ -151,7 +151,7 @@ def test_bench_self_launch_two_ranks_gloo():
 	env = dict(os.environ, STPY_BENCH_BACKEND="gloo")
 	for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
 		env.pop(k, None)
-	r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--n", "4096", "--no-cpu-baseline"],
+	r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--n", "4096", "--full", "--no-cpu-baseline"],
 					   capture_output=True, text=True, timeout=600, env=env, cwd=root)
 	lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
 	assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

@@ -1233,3 +1233,33 @@ def test_kernelized_features_add_data_point_extends_the_normal_equations(S):
 	_, invV, theta = O.kernelized_features_fit(Q, y, 0.2, 1.0)
 	mu_o, std_o = O.kernelized_features_mean_std(O.rff_embed(xt, W, m), invV, theta, 0.2)
 	assert rel_err(N(mu), mu_o) < 1e-8 and rel_err(N(std), std_o) < 1e-8
+
+
+def test_bench_plain_run_times_steps_and_dumps_outputs(S, tmp_path):
+	"""`bench.py` without --full: exactly --steps timed steps, `ms_per_step` in the line, none of the --full figures, and with
+	--dump-outputs the last timed step's mu / std (float64, one row per test point) -- checked against the oracle on the same
+	seeded inputs (tests' synth = bench's synth)."""
+	import json
+	import os
+	import subprocess
+	import sys
+	root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+	n, d, m = 4096, 16, 512
+	env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "STPY_BENCH_FORCE_DIST")}
+	r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--n", str(n), "--m", str(m),
+						"--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+	lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
+	assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+	out = json.loads(lines[0])
+	assert out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "s" and out["higher_is_better"] is False and out["dtype"] == "f64"
+	# the same time twice: `value` in s rounded to 4 decimals, `ms_per_step` in ms rounded to 2 (half a unit of each apart at most)
+	assert out["value"] > 0 and abs(out["ms_per_step"] - out["value"] * 1e3) <= 0.05 + 0.005 + 1e-9
+	assert not {"roofline", "result_check", "extra_configs", "cpu_baseline", "multi_gpu"} & set(out)
+	assert sorted(os.listdir(tmp_path / "out")) == ["mu.npy", "std.npy"]
+	mu, std = np.load(tmp_path / "out" / "mu.npy"), np.load(tmp_path / "out" / "std.npy")
+	assert mu.dtype == np.float64 and std.dtype == np.float64 and mu.shape[0] == m and std.shape[0] == m
+	x, y, xt = synth(n, d, m)
+	spec = se_spec(d ** 0.5)
+	L, alpha = O.fit(x.numpy(), y.numpy(), spec, 0.1)
+	mu_o, std_o = O.mean_std(x.numpy(), L, alpha, xt.numpy(), spec)
+	assert rel_err(mu.reshape(-1), mu_o.reshape(-1)) < 1e-8 and rel_err(std.reshape(-1), std_o.reshape(-1)) < 1e-8

@@ -1317,7 +1317,11 @@ def test_lab_only_cases_in_a_child_interpreter():
 	if not os.path.exists(os.path.join(root, "stpy_amd", "libstpy_hip_lab.so")):
 		pytest.skip("no lab build in this tree (make -C stpy_amd/csrc EXPERIMENTS=1)")
 	env = dict(os.environ, STPY_HIP_LIB="lab")
-	r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_kernels.py"), "-q", "-m", "gpu", "-x", "-rs", "-p", "no:cacheprovider",
+	# exactly the options below (none added through the environment), in an interpreter set up like this one: a suite run that
+	# ignores the user's site-packages (python -s) must not load pytest plugins from there in the child
+	env.pop("PYTEST_ADDOPTS", None)
+	py = [sys.executable] + (["-s"] if sys.flags.no_user_site else [])
+	r = subprocess.run(py + ["-m", "pytest", os.path.join(root, "tests", "test_gpu_kernels.py"), "-q", "-m", "gpu", "-x", "-rs", "-p", "no:cacheprovider",
 						"-k", "test_trsv_handoff_timeout_is_loud or test_potrf_panel_strip_modes"], capture_output=True, text=True, timeout=800, cwd=root, env=env)
 	tail = r.stdout[-3000:] + r.stderr[-2000:]
 	assert r.returncode == 0, tail

@@ -8,11 +8,11 @@ O=$R/gpurun_out/prof_r04
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 cd $R
-echo "== bench line (not profiled)"; python3 bench.py --steps 5 --warmup 2 > $O/bench_line.json 2> $O/bench_line.err || exit 1
+echo "== bench line (not profiled)"; python3 bench.py --full --steps 5 --warmup 2 > $O/bench_line.json 2> $O/bench_line.err || exit 1
 tail -c 600 $O/bench_line.json; echo
-echo "== kernel trace + stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/kt_line.json 2> $O/kt.err || exit 1
-echo "== pmc FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-configs > $O/pmc_fetch.json 2> $O/pmc_fetch.err || exit 1
-echo "== pmc WRITE_SIZE"; rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra-configs > $O/pmc_write.json 2> $O/pmc_write.err || exit 1
+echo "== kernel trace + stats"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra-configs > $O/kt_line.json 2> $O/kt.err || exit 1
+echo "== pmc FETCH_SIZE"; rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o bench -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra-configs > $O/pmc_fetch.json 2> $O/pmc_fetch.err || exit 1
+echo "== pmc WRITE_SIZE"; rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o bench -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra-configs > $O/pmc_write.json 2> $O/pmc_write.err || exit 1
 echo "== gram / rff: kernel stats, then counters"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/gr_kt -o gr -- python3 tools/gram_rff_only.py > $O/gr_kt.log 2>&1 || exit 1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/gr_write -o gr -- python3 tools/gram_rff_only.py > $O/gr_write.log 2>&1 || exit 1
