@@ -258,6 +258,38 @@ int stpy_lml_grad_cov_reduce(int dtype, const void* x, int64_t n, int64_t ldx, i
                              const void* z, int64_t ldz, int p, const void* P, int64_t ldp, void* out, void* stream);
 
 /*
+ * Input gradients of the GP posterior (gauss_procc.py:420-459 mean_gradient_hessian / gradient_mean_var and the
+ * autograd of mean_std through a test tensor with requires_grad; ucb_optimize, :918-963).  One kernel term k = kappa phi,
+ * test points xt (m x ldt) against training points x (n x ldx), scaled differences e = (xt - x_i)[cols] * inv_ls:
+ *   G[t*ldg + cols[k]] (op)= sum_i c_ti d k(xt_t, x_i) / d xt_tk,            c_ti = u_t alpha_i + v_t Wt[t*ldw + i]
+ *   order 2 also: H[(t*ldg + cols[k])*ldg + cols[l]] (op)= sum_i c_ti d^2 k / d xt_tk d xt_tl   (H: m blocks of ldg x ldg)
+ * For the mean gradient alpha = K^-1 y; for the variance gradient Wt = K* K^-1 (stpy_trsm_right_ln).  alpha or Wt may be
+ * NULL (not both); u / v NULL mean 1.  kind, cols, inv_ls, kappa, offset as stpy_gram (the dot-product kinds differentiate
+ * kappa phi(<xt, x_i> scaled)); the kernel values are recomputed from the points by direct differences, K* is not read.
+ * combine: STPY_OUT_SET or STPY_OUT_ADD (the terms of a sum accumulate); cols must not repeat a column.  order 2 is refused
+ * for MATERN12 / MATERN32 (no Hessian at r = 0).  The n range is split into chunks whose partial sums land in `work`
+ * (stpy_gram_grad_workspace_bytes(dtype, m, n, d, order) bytes) and are summed in a fixed order: results are bit-identical
+ * from run to run.  n == 0: nothing is written.
+ */
+int64_t stpy_gram_grad_workspace_bytes(int dtype, int64_t m, int64_t n, int d, int order);
+int stpy_gram_grad(int kind, int dtype, const void* x, int64_t n, int64_t ldx, const void* xt, int64_t m, int64_t ldt,
+                   int d, const int32_t* cols, const void* inv_ls, double kappa, double offset,
+                   const void* alpha, const void* u, const void* Wt, int64_t ldw, const void* v,
+                   int order, int combine, void* G, int64_t ldg, void* H, void* work, int64_t work_bytes, void* stream);
+
+/* B <- B L^-1 (B: m x n rows of right-hand sides), the mirror of stpy_trsm_right_lt: with X = K* L^-T this gives
+ * W^T = X L^-1 = K* K^-1 of the variance gradient.  Runs as B L^-1 = (B J) Lr^-T J, J the order reversal, on the tuned
+ * solve of stpy_trsm_right_lt, with the REVERSED factor Lr = J L^T J (lower triangular) and its inverse diagonal blocks
+ * (block c of winvr = J winv_{nb-1-c}^T J), which stpy_trsm_ln_factor builds once from (L, winv).  The reversed factor is
+ * another n x n matrix plus another winv array: 34 GB + 0.5 GB at n = 65 536 in fp64, on top of the factor itself.
+ * n must be a multiple of 128 (the tile-padded factor of GaussianProcess); work / nb / flags as stpy_trsm_right_lt
+ * (stpy_trsm_workspace_bytes sizes the workspace).  The strict upper triangle of Lr is written as zero. */
+int stpy_trsm_ln_factor(int dtype, int64_t n, const void* L, int64_t ldl, const void* winv, int64_t winv_elems,
+                        void* Lr, int64_t ldlr, void* winvr, void* stream);
+int stpy_trsm_right_ln(int dtype, int64_t m, int64_t n, const void* Lr, int64_t ldlr, const void* winvr, int64_t winv_elems,
+                       void* B, int64_t ldb, int nb, int flags, void* work, int64_t work_bytes, void* stream);
+
+/*
  * Random Fourier features, replaces RFFEmbedding.embed (embedding.py:225-241):
  *   bias == NULL: out[i*ldo + j] = scale * cos(<W_j, x_i>)  for j <  m/2
  *                                  scale * sin(<W_j, x_i>)  for j >= m/2

@@ -11,6 +11,7 @@ What runs where
   X = K* L^-T        stpy_trsm_right_lt     (csrc/solve.hip + csrc/gemm.hip)
   mu, sigma          stpy_predict           (csrc/solve.hip)
   log det, y^T K^-1 y  stpy_logdet_quad     (csrc/solve.hip)
+  d mu, d sigma / dx*  stpy_gram_grad, stpy_trsm_right_ln   (csrc/grad.hip)
 Python only sequences those calls and owns the torch tensors they operate on.
 
 The reference solves with lstsq / LU / slogdet; an SPD solve through the Cholesky factor is the
@@ -52,6 +53,47 @@ class _LogMarginalFn(torch.autograd.Function):
 		grads = ctx.gp._log_marginal_grads(ctx.kernel, ctx.X, ctx.weight, ctx.state, ctx.params)
 		scale = gout.reshape(-1)[0]
 		return (None, None, None, None) + tuple(scale.to(g.device) * g for g in grads)
+
+
+class _PosteriorFn(torch.autograd.Function):
+	"""Autograd node of GaussianProcess.mean_std for a test tensor with requires_grad: forward = the HIP prediction, backward =
+	one stpy_gram_grad launch per kernel term with u = g_mu, v = -g_sigma / sigma (and W^T = X L^-1 only when g_sigma is nonzero)."""
+
+	@staticmethod
+	def forward(ctx, gp, xtest):
+		ctx.set_materialize_grads(False)
+		mu, sigma, state = gp._posterior(xtest.detach())
+		ctx.gp, ctx.state, ctx.like = gp, state, (xtest.device, xtest.dtype, tuple(xtest.shape))
+		return _lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(sigma.reshape(-1, 1), xtest)
+
+	@staticmethod
+	def backward(ctx, gmu, gstd):
+		dev, dt, shape = ctx.like
+		g = ctx.gp._posterior_grad(ctx.state, gmu, gstd)
+		return None, g.to(device=dev, dtype=dt).reshape(shape)
+
+
+class _MeanFn(torch.autograd.Function):
+	"""Autograd node of GaussianProcess.mean (K* alpha): backward = stpy_gram_grad with u = g_mu on alpha."""
+
+	@staticmethod
+	def forward(ctx, gp, xtest):
+		ctx.gp, ctx.like = gp, (xtest.device, xtest.dtype, tuple(xtest.shape))
+		ctx.xt = _lib.to_device(xtest.detach(), gp._xd.dtype)
+		return gp._mean_value(xtest.detach())
+
+	@staticmethod
+	def backward(ctx, gmu):
+		dev, dt, shape = ctx.like
+		gp = ctx.gp
+		G = torch.zeros(ctx.xt.shape, dtype=ctx.xt.dtype, device=ctx.xt.device)
+		u = _lib.to_device(gmu, ctx.xt.dtype).reshape(-1).contiguous()
+		gp.kernel_object._grad_into(gp._xd, ctx.xt, G, alpha=gp._alpha.reshape(-1).contiguous(), u=u)
+		return None, G.to(device=dev, dtype=dt).reshape(shape)
+
+
+def _wants_grad(xtest):
+	return torch.is_tensor(xtest) and xtest.requires_grad and torch.is_grad_enabled()
 
 
 def _tile_pad(n):
@@ -108,6 +150,8 @@ class GaussianProcess(Estimator):
 		self._z = None          # L^-1 y
 		self._Sigma = None
 		self._alpha_cache = None
+		self._Lr = None         # reversed factor J L^T J and its inverse diagonal blocks (stpy_trsm_ln_factor): built on the first
+		self._winvr = None      # variance gradient after a fit, dropped on refit
 
 	# ------------------------------------------------------------------ small API mirrors
 	def description(self):
@@ -253,6 +297,7 @@ class GaussianProcess(Estimator):
 		# object that takes the prior branch instead of one that reports fitted=True with no factor behind it
 		self.fitted = False
 		self._L = self._winv = self._z = self._alpha_cache = None       # release the previous factor before allocating the next
+		self._Lr = self._winvr = None
 		L, winv, info = self._factor(self._xd, None, Sigma, defer_check=True)
 		z = self._forward_y(L, winv, self._yd)
 		# A = K^-1 y is part of the fitted state the reference leaves behind (gauss_procc.py:376): computed
@@ -358,6 +403,13 @@ class GaussianProcess(Estimator):
 	def mean_std(self, xtest, full=False, reuse=False):
 		"""gauss_procc.py:310-334: chunks of ``max_size`` test points against the resident factor."""
 		m = xtest.size()[0]
+		if _wants_grad(xtest):
+			if full:
+				raise ValueError("mean_std(full=True) has no input gradient: pass a test tensor without requires_grad")
+			parts = [_PosteriorFn.apply(self, xtest[i0:i0 + self.max_size]) for i0 in range(0, m, self.max_size)]
+			if len(parts) == 1:
+				return parts[0]
+			return torch.cat([p[0] for p in parts], dim=0), torch.cat([p[1] for p in parts], dim=0)
 		if m < self.max_size or full:
 			return self.mean_std_sub(xtest, full=full, reuse=reuse)
 		dtype = self._xd.dtype if self.fitted else (xtest.dtype if xtest.dtype in (torch.float32, torch.float64) else torch.float64)
@@ -391,28 +443,14 @@ class GaussianProcess(Estimator):
 
 		xd = self._xd
 		xt = _lib.to_device(xtest, xd.dtype)
-		m, n = xt.shape[0], self.n
+		if not full:
+			mu, sigma, _ = self._predict(xt)
+			return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(sigma.reshape(-1, 1), xtest))
+		m, n = xt.shape[0], self._L.shape[0]
 		dt = _lib.dtype_code(xd.dtype)
 		st = _lib.stream_ptr
-		n0, n = n, self._L.shape[0]                                     # n: order of the (tile-padded) factor
-		mp = _tile_pad(m)                                               # rows of K* padded to the tile as well (zero rows)
-		X = torch.empty((mp, n), dtype=xd.dtype, device=xd.device)
-		ko._kernel_into(xd, xt, X[:m, :n0])                             # K* = k(x, xtest): (M, N)   :346
-		if n > n0:
-			X[:, n0:].zero_()
-		if mp > m:
-			X[m:, :].zero_()
-		tw = torch.empty((int(lib.stpy_trsm_workspace_bytes(dt, mp, n, self.nb)),), dtype=torch.uint8, device=X.device)
-		_lib.check(lib.stpy_trsm_right_lt(dt, mp, n, _lib.ptr(self._L), _lib.ld(self._L), _lib.ptr(self._winv), self._winv.numel(),
-										  _lib.ptr(X), _lib.ld(X), self.nb, 0, _lib.ptr(tw), tw.numel() * tw.element_size(), st()), "stpy_trsm_right_lt")   # X = K* L^-T
+		X = self._solve_kstar(xt)
 		mu = torch.empty((m,), dtype=xd.dtype, device=xd.device)
-		if not full:
-			kd = torch.empty((m,), dtype=xd.dtype, device=xd.device)
-			ko._diag_into(xt, kd)                                       # diag k(x*, x*)           :347
-			sigma = torch.empty((m,), dtype=xd.dtype, device=xd.device)
-			_lib.check(lib.stpy_predict(dt, m, n, _lib.ptr(X), _lib.ld(X), _lib.ptr(self._z), _lib.ptr(kd), _lib.ptr(mu),
-										_lib.ptr(sigma), 1 if self.clamp_variance else 0, st()), "stpy_predict")
-			return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(sigma.reshape(-1, 1), xtest))
 		_lib.check(lib.stpy_predict(dt, m, n, _lib.ptr(X), _lib.ld(X), _lib.ptr(self._z), None, _lib.ptr(mu),
 									None, 0, st()), "stpy_predict")
 		cov = torch.empty((m, m), dtype=xd.dtype, device=xd.device)
@@ -421,8 +459,182 @@ class GaussianProcess(Estimator):
 									_lib.ld(cov), 1, 0, st()), "stpy_gemm_nt")                    # K** - X X^T  :396-399
 		return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(cov, xtest))
 
+	def _solve_kstar(self, xt):
+		"""X = K* L^-T (tile-padded: (mp, npad), zero rows past m and zero columns past n)."""
+		lib = _lib.load()
+		xd = self._xd
+		m, n0, n = xt.shape[0], self.n, self._L.shape[0]                # n: order of the (tile-padded) factor
+		dt = _lib.dtype_code(xd.dtype)
+		mp = _tile_pad(m)                                               # rows of K* padded to the tile as well (zero rows)
+		X = torch.empty((mp, n), dtype=xd.dtype, device=xd.device)
+		self.kernel_object._kernel_into(xd, xt, X[:m, :n0])             # K* = k(x, xtest): (M, N)   :346
+		if n > n0:
+			X[:, n0:].zero_()
+		if mp > m:
+			X[m:, :].zero_()
+		tw = torch.empty((int(lib.stpy_trsm_workspace_bytes(dt, mp, n, self.nb)),), dtype=torch.uint8, device=X.device)
+		_lib.check(lib.stpy_trsm_right_lt(dt, mp, n, _lib.ptr(self._L), _lib.ld(self._L), _lib.ptr(self._winv), self._winv.numel(),
+										  _lib.ptr(X), _lib.ld(X), self.nb, 0, _lib.ptr(tw), tw.numel() * tw.element_size(), _lib.stream_ptr()), "stpy_trsm_right_lt")   # X = K* L^-T
+		return X
+
+	def _predict(self, xt):
+		"""mu, sigma (M,) and X = K* L^-T for device test points against the resident factor (gauss_procc.py:336-401, squared loss)."""
+		lib = _lib.load()
+		xd = self._xd
+		m, n = xt.shape[0], self._L.shape[0]
+		dt = _lib.dtype_code(xd.dtype)
+		X = self._solve_kstar(xt)
+		mu = torch.empty((m,), dtype=xd.dtype, device=xd.device)
+		kd = torch.empty((m,), dtype=xd.dtype, device=xd.device)
+		self.kernel_object._diag_into(xt, kd)                           # diag k(x*, x*)           :347
+		sigma = torch.empty((m,), dtype=xd.dtype, device=xd.device)
+		_lib.check(lib.stpy_predict(dt, m, n, _lib.ptr(X), _lib.ld(X), _lib.ptr(self._z), _lib.ptr(kd), _lib.ptr(mu),
+									_lib.ptr(sigma), 1 if self.clamp_variance else 0, _lib.stream_ptr()), "stpy_predict")
+		return mu, sigma, X
+
+	# ------------------------------------------------------------------ input gradients (gauss_procc.py:420-459, :918-963)
+	def _posterior(self, xtest):
+		"""mu, sigma (M,) on the device and what their input gradient needs: (xt, X or None, sigma)."""
+		if not self.fitted:
+			xt = _lib.to_device(xtest)
+			mu, sd = self.mean_std_sub(xt)
+			sigma = sd.reshape(-1)
+			return mu.reshape(-1), sigma, (xt, None, sigma)
+		xt = _lib.to_device(xtest, self._xd.dtype)
+		mu, sigma, X = self._predict(xt)
+		return mu, sigma, (xt, X, sigma)
+
+	def _reversed_factor(self):
+		"""J L^T J and its inverse diagonal blocks for B L^-1 (stpy_trsm_ln_factor): another N x N matrix, built once per fit."""
+		if getattr(self, "_Lr", None) is None:
+			lib = _lib.load()
+			L = self._L
+			Lr = torch.empty_like(L)
+			winvr = torch.empty_like(self._winv)
+			_lib.check(lib.stpy_trsm_ln_factor(_lib.dtype_code(L.dtype), L.shape[0], _lib.ptr(L), _lib.ld(L), _lib.ptr(self._winv), self._winv.numel(),
+											   _lib.ptr(Lr), _lib.ld(Lr), _lib.ptr(winvr), _lib.stream_ptr()), "stpy_trsm_ln_factor")
+			self._Lr, self._winvr = Lr, winvr
+		return self._Lr, self._winvr
+
+	def _weights_t(self, X):
+		"""W^T = K* K^-1 = X L^-1 (in place over a copy of X): the variance gradient's coefficients, (mp, npad)."""
+		lib = _lib.load()
+		Lr, winvr = self._reversed_factor()
+		W = X.clone()
+		mp, n = W.shape
+		dt = _lib.dtype_code(W.dtype)
+		tw = torch.empty((int(lib.stpy_trsm_workspace_bytes(dt, mp, n, self.nb)),), dtype=torch.uint8, device=W.device)
+		_lib.check(lib.stpy_trsm_right_ln(dt, mp, n, _lib.ptr(Lr), _lib.ld(Lr), _lib.ptr(winvr), winvr.numel(), _lib.ptr(W), _lib.ld(W),
+										  self.nb, 0, _lib.ptr(tw), tw.numel() * tw.element_size(), _lib.stream_ptr()), "stpy_trsm_right_ln")
+		return W
+
+	def _posterior_grad(self, state, gmu, gstd):
+		"""sum_t gmu_t grad mu(xt_t) + gstd_t grad sigma(xt_t), one row per test point: (M, d) on the device.
+		grad sigma = (grad_x k(x, x) - 2 sum_i w_i grad_x k(x, x_i)) / (2 sigma), 0 where sigma is 0."""
+		xt, X, sigma = state
+		ko = self.kernel_object
+		G = torch.zeros(xt.shape, dtype=xt.dtype, device=xt.device)
+		u = None if gmu is None else _lib.to_device(gmu, xt.dtype).reshape(-1).contiguous()
+		gs = None if gstd is None else _lib.to_device(gstd, xt.dtype).reshape(-1)
+		if gs is not None and not bool((gs != 0).any()):
+			gs = None
+		if gs is not None:
+			pos = sigma > 0
+			safe = torch.where(pos, sigma, torch.ones_like(sigma))
+			v = torch.where(pos, -gs / safe, torch.zeros_like(gs)).contiguous()
+			self_coef = torch.where(pos, gs / (2.0 * safe), torch.zeros_like(gs))
+		if X is not None and (u is not None or gs is not None):
+			Wt = self._weights_t(X) if gs is not None else None
+			ko._grad_into(self._xd, xt, G, alpha=self._alpha.reshape(-1).contiguous() if u is not None else None, u=u,
+						  Wt=Wt, v=v if gs is not None else None)
+		if gs is not None:
+			ko._self_grad_into(xt, self_coef, G)
+		return G
+
+	def mean_std_grad(self, xtest):
+		"""Batched input gradients of the posterior: (d mu, d std), each (M, d), where the inputs live."""
+		mu, sigma, state = self._posterior(xtest.detach() if torch.is_tensor(xtest) else xtest)
+		ones = torch.ones_like(sigma)
+		dmu = self._posterior_grad(state, ones, None)
+		dstd = self._posterior_grad(state, None, ones)
+		return _lib.like_input(dmu, xtest), _lib.like_input(dstd, xtest)
+
+	def mean_gradient_hessian(self, xtest, hessian=False):
+		"""gauss_procc.py:444-459: the gradient (d,) of the posterior mean at the first row of xtest, and with ``hessian`` its
+		Hessian (d, d) -- stpy_gram_grad with order 2 on alpha."""
+		ko = self.kernel_object
+		x1 = xtest[:1].detach() if torch.is_tensor(xtest) else xtest[:1]
+		if not self.fitted:
+			d = x1.shape[1]
+			g, h = torch.zeros(d, dtype=torch.float64), torch.zeros((d, d), dtype=torch.float64)
+			return [g, h] if hessian else g
+		xt = _lib.to_device(x1, self._xd.dtype)
+		d = xt.shape[1]
+		G = torch.zeros((1, d), dtype=xt.dtype, device=xt.device)
+		H = torch.zeros((1, d, d), dtype=xt.dtype, device=xt.device) if hessian else None
+		ko._grad_into(self._xd, xt, G, alpha=self._alpha.reshape(-1).contiguous(), H=H)
+		g = _lib.like_input(G[0], xtest)
+		if not hessian:
+			return g
+		return [g, _lib.like_input(H[0], xtest)]
+
+	def gradient_mean_var(self, point, hessian=False):
+		"""gauss_procc.py:420-442: the gradient of the posterior mean at one point.  The reference's hessian=True branch calls
+		KernelFunction.get_2_der / get_1_der, which do not exist there (it raises AttributeError)."""
+		if hessian:
+			raise NotImplementedError("gradient_mean_var(hessian=True): the reference calls kernel get_2_der / get_1_der, which do not "
+									  "exist in stpy; use mean_gradient_hessian(x, hessian=True) for the mean's Hessian")
+		return self.mean_gradient_hessian(point, hessian=False)
+
+	def ucb_optimize(self, beta, multistart=25, lcb=False):
+		"""
+		gauss_procc.py:918-963: maximise mu + sqrt(beta) sigma (mu - sqrt(beta) sigma with ``lcb``) over ``self.bounds`` from
+		``multistart`` uniform starts, drawn with the reference's np.random calls in its order.  All starts run as ONE L-BFGS-B
+		problem over the stacked points (the objective is a sum of independent terms), so every step is one batched device
+		evaluation of the values and their analytic gradients.  Returns (solution, value) of the best start.
+		"""
+		from scipy.optimize import minimize
+		if self.bounds is None:
+			raise ValueError("ucb_optimize needs box bounds: set GaussianProcess.bounds to a list of (low, high) per coordinate")
+		mybounds = self.bounds
+		starts = []
+		for _ in range(multistart):
+			x0 = np.random.randn(self.d)
+			for i in range(self.d):
+				x0[i] = np.random.uniform(mybounds[i][0], mybounds[i][1])
+			starts.append(x0)
+		S, d = len(starts), self.d
+		sign = -1.0 if lcb else 1.0
+		sb = float(np.sqrt(beta))
+		dev = self._xd.device if self._xd is not None else _lib.device()
+		dtype = self._xd.dtype if self._xd is not None else torch.float64
+
+		def evaluate(z):
+			xt = torch.from_numpy(np.ascontiguousarray(z.reshape(S, d))).to(device=dev, dtype=dtype)
+			mu, sigma, state = self._posterior(xt)
+			val = mu + sign * sb * sigma
+			return val, state
+
+		def fun(z):
+			val, state = evaluate(z)
+			g = self._posterior_grad(state, torch.ones_like(val), torch.full_like(val, sign * sb))
+			return -float(val.sum().item()), -g.double().cpu().numpy().reshape(-1)
+
+		res = minimize(fun, np.concatenate(starts), method="L-BFGS-B", jac=True, bounds=list(mybounds) * S,
+					   options=dict(maxiter=15000, ftol=1e-15, gtol=1e-10))
+		sol = res.x.reshape(S, d)
+		vals, _ = evaluate(res.x)
+		vals = vals.double().cpu().numpy()
+		index = int(np.argmax(vals))
+		return (torch.from_numpy(sol[index].copy()), torch.tensor(float(vals[index]), dtype=torch.float64))
+
 	def mean(self, xtest):
 		"""gauss_procc.py:403-418: K* alpha."""
+		if _wants_grad(xtest):
+			return _MeanFn.apply(self, xtest)
+		return self._mean_value(xtest)
+
+	def _mean_value(self, xtest):
 		lib = _lib.load()
 		xd = self._xd
 		xt = _lib.to_device(xtest, xd.dtype)

@@ -513,6 +513,14 @@ class KernelizedFeatures(GaussianProcess):
 
 	mean_var = mean_std
 
+	# the input gradients of GaussianProcess differentiate the kernel-space posterior; this model's posterior lives in the
+	# feature space of the embedding, so the inherited methods would return numbers of the wrong model
+	def _no_input_gradients(self, *args, **kwargs):
+		raise NotImplementedError("KernelizedFeatures has no input gradients (mean_std_grad, mean_gradient_hessian, gradient_mean_var, "
+								  "ucb_optimize are GaussianProcess methods: they differentiate the kernel, not the embedding)")
+
+	mean_std_grad = mean_gradient_hessian = gradient_mean_var = ucb_optimize = _no_input_gradients
+
 	def ucb(self, xtest, delta=0.1):
 		mu, std = self.mean_std(xtest)
 		return mu + np.sqrt(self.beta(delta=delta)) * std

@@ -366,9 +366,12 @@ class KernelFunction:
 		self._kernel_into(ad, bd, out, kwargs)
 		return _lib.like_input(out, a)
 
-	def _diag_into(self, x, out, kwargs=None):
+	def _diag_into(self, x, out, kwargs=None, items=None):
 		lib = _lib.load()
-		items = self._resolve(dict(kwargs) if kwargs else {})
+		if items is None:
+			items = self._resolve(dict(kwargs) if kwargs else {})
+		elif items and items[0]['op'] != "-":
+			items = [dict(items[0], op="-")] + list(items[1:])
 		dt = _lib.dtype_code(out.dtype)
 		tmp = None
 		for l in self._plan(items):
@@ -395,6 +398,161 @@ class KernelFunction:
 		out = torch.empty((xd.shape[0],), dtype=xd.dtype, device=xd.device)
 		self._diag_into(xd, out, kwargs)
 		return _lib.like_input(out, x)
+
+	# ------------------------------------------------------------------ input gradients (gauss_procc.py:420-459, :918-963)
+	@staticmethod
+	def _factors(items, i):
+		"""The factors item i is multiplied with under the * algebra (d K / d K_i, as in the evidence gradient): the chain before it
+		when its own operation is *, and every later item joined by *."""
+		factors = []
+		if items[i]['op'] == "*" and i > 0:
+			factors.append(items[:i])
+		for j in range(i + 1, len(items)):
+			if items[j]['op'] == "*":
+				factors.append([items[j]])
+		return factors
+
+	@staticmethod
+	def _term_name(term):
+		kind = term['kind'] & 0xff
+		return {_lib.K_SE: "squared exponential", _lib.K_MATERN12: "Matern nu=0.5", _lib.K_MATERN32: "Matern nu=1.5",
+				_lib.K_MATERN52: "Matern nu=2.5", _lib.K_LINEAR: "linear", _lib.K_POLY: "polynomial"}[kind] + \
+			(" (full covariance)" if term['premap'] is not None else "")
+
+	def _grad_into(self, x, xt, G, alpha=None, u=None, Wt=None, v=None, H=None, kwargs=None):
+		"""
+		G (m, D) <- d/dxt_t sum_i c_ti k(xt_t, x_i) with c_ti = u_t alpha_i + v_t Wt[t, i] (u / v None: 1; alpha or Wt None: that
+		part is absent), and with H (m, D, D) also the second derivatives.  x (n, D), xt (m, D), Wt (m, >= n) are device tensors.
+		Every term is one stpy_gram_grad launch that adds into G; the columns of a grouped term are scattered by the kernel.
+		A full-covariance term is differentiated in the mapped coordinates z = x[:, group] cov and brought back by the chain rule
+		(G[:, group] += G_z cov^T, one stpy_gemm_nt); the factors of a * item enter through the coefficients:
+		C o prod_{l != j} K_l, formed with stpy_gram's multiply combine.
+		"""
+		lib = _lib.load()
+		items = self._resolve(dict(kwargs) if kwargs else {})
+		if items and items[0]['op'] != "-":
+			items = [dict(items[0], op="-")] + list(items[1:])
+		order = 1 if H is None else 2
+		if H is not None:
+			for it in items:
+				if it['op'] == "*":
+					raise NotImplementedError("Hessian of a product kernel (item joined by '*') is not implemented on the device")
+				for t in it['terms']:
+					if t['kind'] in (_lib.K_MATERN12, _lib.K_MATERN32):
+						raise NotImplementedError("Hessian of the %s term is not defined (singular at r = 0)" % self._term_name(t))
+		G.zero_()
+		if H is not None:
+			H.zero_()
+		m, n = xt.shape[0], x.shape[0]
+		if m == 0 or n == 0:
+			return G
+		dt = _lib.dtype_code(G.dtype)
+		dev = G.device
+		has_mul = any(it['op'] == "*" for it in items)
+		C = None
+		if has_mul:
+			C = torch.zeros((m, n), dtype=G.dtype, device=dev)
+			if alpha is not None:
+				C += (u.reshape(-1, 1) if u is not None else 1.0) * alpha.reshape(1, -1)[:, :n]
+			if Wt is not None:
+				C += (v.reshape(-1, 1) if v is not None else 1.0) * Wt[:m, :n]
+		for i, it in enumerate(items):
+			factors = self._factors(items, i) if has_mul else []
+			if factors:
+				Ci = C.clone()
+				for fac in factors:
+					if len(fac) == 1 and len(fac[0]['terms']) == 1:
+						self._run_items([dict(fac[0], op="*")], x, xt, Ci, first_is_set=False)
+						continue
+					tmp = torch.empty((m, n), dtype=G.dtype, device=dev)
+					self._run_items(fac, x, xt, tmp)
+					_lib.check(lib.stpy_combine(dt, m, n, _lib.ptr(Ci), Ci.stride(0), _lib.ptr(tmp), tmp.stride(0), _lib.OUT_MUL, 0.0,
+												_lib.stream_ptr()), "stpy_combine")
+				coef = (None, None, Ci, None)
+			elif has_mul:
+				coef = (None, None, C, None)
+			else:
+				coef = (alpha, u, Wt, v)
+			for t in it['terms']:
+				self._term_grad(t, x, xt, coef, G, H, order)
+		return G
+
+	def _term_grad(self, t, x, xt, coef, G, H, order):
+		lib = _lib.load()
+		alpha, u, Wt, v = coef
+		m, n = xt.shape[0], x.shape[0]
+		dt = _lib.dtype_code(G.dtype)
+		dev = G.device
+		if t['premap'] is not None:
+			group = t['group']
+			zx = self._premap(x, group, t['premap'])
+			zt = self._premap(xt, group, t['premap'])
+			p = zx.shape[1]
+			Gz = torch.empty((m, p), dtype=G.dtype, device=dev)
+			Hz = torch.empty((m, p, p), dtype=G.dtype, device=dev) if H is not None else None
+			self._launch_grad(t['kind'], zx, zt, p, None, [1.0] * p, t['kappa'], t['offset'], coef, _lib.OUT_SET, Gz, Hz, order)
+			cov = t['premap'].to(device=dev, dtype=G.dtype).contiguous()            # (dg, p): G_z cov^T is the NT product of G_z and cov
+			Gx = torch.empty((m, cov.shape[0]), dtype=G.dtype, device=dev)
+			_lib.check(lib.stpy_gemm_nt(dt, m, cov.shape[0], p, _lib.ptr(Gz), Gz.stride(0), _lib.ptr(cov), cov.stride(0), _lib.ptr(Gx), Gx.stride(0),
+										0, 0, _lib.stream_ptr()), "stpy_gemm_nt")
+			gi = torch.as_tensor(group, dtype=torch.long, device=dev)
+			G.index_add_(1, gi, Gx)
+			if H is not None:                   # cov H_z cov^T per point (d x d, single points): small, plumbing
+				Hx = torch.einsum("ap,tpq,bq->tab", cov, Hz, cov)
+				H[:, gi.reshape(-1, 1), gi.reshape(1, -1)] += Hx
+			return
+		group = t['group']
+		cols = None if group == list(range(x.shape[1])) else _dev_const(group, None, dev, int32=True)
+		self._launch_grad(t['kind'], x, xt, len(group), cols, t['inv_ls'], t['kappa'], t['offset'], coef, _lib.OUT_ADD, G, H, order)
+
+	@staticmethod
+	def _launch_grad(kind, x, xt, d, cols, inv_ls, kappa, offset, coef, combine, G, H, order):
+		lib = _lib.load()
+		alpha, u, Wt, v = coef
+		m, n = xt.shape[0], x.shape[0]
+		dt = _lib.dtype_code(G.dtype)
+		il = _dev_const(inv_ls, G.dtype, G.device)
+		work = torch.empty((int(lib.stpy_gram_grad_workspace_bytes(dt, m, n, d, order)),), dtype=torch.uint8, device=G.device)
+		rc = lib.stpy_gram_grad(kind, dt, _lib.ptr(x), n, x.stride(0), _lib.ptr(xt), m, xt.stride(0), d, _lib.ptr(cols), _lib.ptr(il),
+								float(kappa), float(offset), _lib.ptr(alpha), _lib.ptr(u), _lib.ptr(Wt), Wt.stride(0) if Wt is not None else 0,
+								_lib.ptr(v), order, combine, _lib.ptr(G), G.stride(0), _lib.ptr(H), _lib.ptr(work), work.numel(), _lib.stream_ptr())
+		_lib.check(rc, "stpy_gram_grad")
+
+	def _self_grad_into(self, xt, coef, G, kwargs=None):
+		"""G[t] += coef_t * grad_x k(x, x) at x = xt_t: zero for stationary terms (k(x, x) = kappa); for the dot-product terms
+		2 kappa phi'(s) inv_ls^2 x with s = |x * inv_ls|^2 (+ offset), the product rule over * items with the k(x, x) of the other
+		factors (stpy_gram_diag).  O(m D) elementwise work on (m, D) tensors."""
+		items = self._resolve(dict(kwargs) if kwargs else {})
+		if items and items[0]['op'] != "-":
+			items = [dict(items[0], op="-")] + list(items[1:])
+		m = xt.shape[0]
+		for i, it in enumerate(items):
+			gi = None
+			for t in it['terms']:
+				kind = t['kind'] & 0xff
+				if t['premap'] is not None or kind not in (_lib.K_LINEAR, _lib.K_POLY):
+					continue
+				cols = torch.as_tensor(t['group'], dtype=torch.long, device=xt.device)
+				il = torch.as_tensor(t['inv_ls'], dtype=xt.dtype, device=xt.device)
+				xs = xt[:, cols] * il
+				if kind == _lib.K_LINEAR:
+					f = torch.full((m, 1), 2.0 * t['kappa'], dtype=xt.dtype, device=xt.device)
+				else:
+					p = t['kind'] >> 8
+					b = (xs * xs).sum(dim=1, keepdim=True) + t['offset']
+					f = 2.0 * t['kappa'] * p * b ** (p - 1)
+				g = torch.zeros_like(G)
+				g[:, cols] = f * xs * il
+				gi = g if gi is None else gi + g
+			if gi is None:
+				continue
+			w = coef.reshape(-1, 1)
+			for fac in self._factors(items, i):
+				dv = torch.empty((m,), dtype=xt.dtype, device=xt.device)
+				self._diag_into(xt, dv, items=fac)
+				w = w * dv.reshape(-1, 1)
+			G += w * gi
+		return G
 
 	# ------------------------------------------------------------------ finite-dimensional cases (kernels.py:263-273)
 	def embed(self, x):

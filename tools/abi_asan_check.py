@@ -16,7 +16,7 @@ import textwrap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "stpy_amd", "csrc")
-SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce"]
+SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce", "grad"]
 
 CHILD = r'''
 import ctypes, sys
@@ -100,6 +100,16 @@ neg(lib.stpy_lml_grad_reduce(0, P, 4, 4, 2, N, P, P, 2, N, P, N), "lml_grad_redu
 neg(lib.stpy_lml_grad_reduce(0, N, 4, 4, 2, N, P, P, 3, N, P, N), "lml_grad_reduce null x")
 neg(lib.stpy_lml_grad_cov_reduce(0, P, 4, 4, 2, N, N, 2, 2, P, 3, P, N), "lml_grad_cov_reduce null z")
 neg(lib.stpy_lml_grad_cov_reduce(0, P, 4, 4, 2, N, P, 2, 2, P, 2, P, N), "lml_grad_cov_reduce ldp < p + 1")
+# ---- input gradients
+neg(lib.stpy_gram_grad(9, 0, P, 4, 4, P, 4, 4, 2, N, P, 1.0, 0.0, P, N, N, 0, N, 1, 0, P, 4, N, P, 1 << 20, N), "gram_grad unknown kind")
+neg(lib.stpy_gram_grad(0, 0, P, 4, 4, P, 4, 4, 0, N, P, 1.0, 0.0, P, N, N, 0, N, 1, 0, P, 4, N, P, 1 << 20, N), "gram_grad d = 0")
+neg(lib.stpy_gram_grad(1, 0, P, 4, 4, P, 4, 4, 2, N, P, 1.0, 0.0, P, N, N, 0, N, 2, 0, P, 4, P, P, 1 << 20, N), "gram_grad Matern 1/2 Hessian")
+neg(lib.stpy_gram_grad(0, 0, P, 4, 4, P, 4, 4, 2, N, P, 1.0, 0.0, P, N, N, 0, N, 1, 0, N, 4, N, P, 1 << 20, N), "gram_grad null G")
+neg(lib.stpy_gram_grad(0, 0, P, 4, 4, P, 4, 4, 2, N, P, 1.0, 0.0, P, N, N, 0, N, 1, 0, P, 4, N, P, 8, N), "gram_grad undersized workspace")
+zero(lib.stpy_gram_grad(0, 0, N, 0, 4, N, 4, 4, 2, N, N, 1.0, 0.0, N, N, N, 0, N, 1, 0, N, 4, N, N, 0, N), "gram_grad empty")
+neg(lib.stpy_trsm_ln_factor(0, 200, P, 200, P, 1 << 20, P, 200, P, N), "trsm_ln_factor n not tile-aligned")
+neg(lib.stpy_trsm_right_ln(0, 8, 256, N, 256, P, 1 << 20, P, 256, 0, 0, N, 0, N), "trsm_right_ln null L")
+neg(lib.stpy_trsm_right_ln(0, 8, 256, P, 256, P, 10, P, 256, 0, 0, N, 0, N), "trsm_right_ln winv too small")
 # ---- RFF
 assert lib.stpy_rff_workspace_bytes(1, 262144, 64, 32768) > 0 and lib.stpy_rff_workspace_bytes(0, 100, 5, 64) == 0
 neg(lib.stpy_rff_embed(1, N, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 0, N, 0, N), "rff null x")
