@@ -25,7 +25,7 @@
  *         stream must be issued by one thread at a time (they are ordered by the stream, like any HIP work); with them 64 bytes
  *         of device memory (the ticket / counter words of the one-launch vector solve), the library's only allocation;
  *       * the launch profiler's record table (stpy_profile_*), guarded by a mutex, off by default;
- *       * the nine ROUTE switches of stpy_tune (which shipped kernel serves a call where the library normally decides by
+ *       * the ten ROUTE switches of stpy_tune (which shipped kernel serves a call where the library normally decides by
  *         size): process-wide integers read at launch time, never written by the shipped host code -- tests/ use them to
  *         reach every shipped path at small sizes; they must not be changed while another thread is inside the library.
  *         Behaviour a caller may legitimately want per call is a `flags` argument instead (STPY_FLAG_*).  The timing
@@ -121,6 +121,28 @@ int64_t stpy_potrf_workspace_bytes(int dtype, int64_t n, int nb);
 int64_t stpy_potrf_winv_elems(int64_t n);
 int stpy_potrf(int dtype, int64_t n, void* A, int64_t lda, void* winv, int64_t winv_elems,
                void* work, int64_t work_bytes, int nb, int flags, int32_t* info_dev, void* stream);
+
+/*
+ * Bordered Cholesky: extend a resident factor by k rows (GaussianProcess.add_data_point(iterative=True); the "iterative" branch of
+ * fit_gp, gauss_procc.py:136-177, which the reference leaves a stub).  n1 = n0 + k, n1p = n1 rounded up to a multiple of 128,
+ * t0 = 128 * floor(n0 / 128).
+ *   on entry: rows [0, n0) of A's lower triangle hold a factor from stpy_potrf (or an earlier append) on the tile-padded layout
+ *             (winv: its inverse diagonal blocks); rows [n0, n1), columns [0, n1), lower part: the new rows of K + s^2 I;
+ *             z (may be NULL): L11^-1 y_old in [0, n0); y: the k new targets (device, read only when z is given).
+ *   on exit:  A[0:n1p, 0:n1p] has the layout stpy_potrf leaves for the bordered matrix -- [L21 L22] in rows [n0, n1), zeros in
+ *             columns (r, n1p) of each new row r, identity rows [n1, n1p) -- so every consumer (stpy_trsv, stpy_trsm_right_lt,
+ *             stpy_predict, stpy_logdet_quad, stpy_trsm_ln_factor, stpy_potri) runs on it with n = n1p; winv blocks
+ *             [t0/128, n1p/128) hold inverse(L_cc); z[n0:n1) = L22^-1 (y - L21 z1), z[n1:n1p) = 0; *info_dev = 0, or the 1-based
+ *             global index of the first non-positive pivot.
+ * Rows [0, n0) of A and the winv blocks below t0 are not written.  L21 = K21 L11^-T streams L11 once per 8 (fp64) / 16 (fp32) right-hand sides:
+ * a one-launch dataflow solve (the hand-off protocol of stpy_trsv, whose sticky error word stpy_async_status reports); more than 32
+ * (stpy_tune key 34) on the MFMA block solve of stpy_trsm_right_lt.  S = K22 + s^2 I - L21 L21^T (stpy_gemm_nt, lower tiles) is
+ * factored by one workgroup for k <= 128 and by stpy_potrf on a padded copy above.  Every sum has a fixed order: bit-reproducible.
+ * lda >= n1p (-5), winv_elems >= stpy_potrf_winv_elems(n1p) (-21), work_bytes >= the query (-20); n0 >= 1, k >= 1.
+ */
+int64_t stpy_potrf_append_workspace_bytes(int dtype, int64_t n0, int64_t k);
+int stpy_potrf_append(int dtype, int64_t n0, int64_t k, void* A, int64_t lda, void* winv, int64_t winv_elems, void* z, const void* y,
+                      void* work, int64_t work_bytes, int32_t* info_dev, void* stream);
 
 /* B <- B L^-T for B: m x n row-major (rows = right-hand sides).  With B = K* (M x N) this is
  * V^T = (L^-1 K*^T)^T of the variance term, gauss_procc.py:378,392.  From 2048 rows on: recursive
@@ -338,6 +360,8 @@ int stpy_async_status(void* stream);
  *      fused epilogue of the MFMA GEMM
  *   30 plain / lower-only products (both types) of at most this many 128 x 128 tiles (and K >= 64) run as 32 x 128 slivers, four
  *      times the workgroups of the tile kernels (3200; 0 = never) -- the small trailing updates at the end of every factorisation
+ *   34 bordered factor (stpy_potrf_append): more new rows than this take the MFMA block solve for L21 instead of the dataflow
+ *      solve (32; 0 = always the MFMA solve; key 16 = 0 also forces it)
  *   32 fp32 factorisation: 1 = each finished panel is split ONCE into three bf16 planes in the workspace and its trailing updates of
  *      2048 rows and more run from those planes (gemm_bf3p.hip); 0 = every tile of an update splits its operands on the fly (key 26's
  *      kernel).  Both give bit-identical factors.

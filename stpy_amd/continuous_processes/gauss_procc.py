@@ -150,6 +150,7 @@ class GaussianProcess(Estimator):
 		self._z = None          # L^-1 y
 		self._Sigma = None
 		self._alpha_cache = None
+		self._Lbuf = None       # the buffer _L is a leading view of after add_data_point(iterative=True) (capacity for more rows)
 		self._Lr = None         # reversed factor J L^T J and its inverse diagonal blocks (stpy_trsm_ln_factor): built on the first
 		self._winvr = None      # variance gradient after a fit, dropped on refit
 
@@ -166,8 +167,13 @@ class GaussianProcess(Estimator):
 	def residuals(self, x, y):
 		return self.mean(x) - y
 
-	def add_data_point(self, x, y, Sigma=None):
-		"""gauss_procc.py:100-111: concatenate and refit from scratch."""
+	def add_data_point(self, x, y, Sigma=None, iterative=False):
+		"""gauss_procc.py:100-111: concatenate and refit from scratch.  ``iterative=True`` extends the resident factor by the new rows
+		instead (stpy_potrf_append: one pass over L for a handful of points) whenever that is the same mathematics -- same kernel
+		parameters and noise as the factor, no explicit Sigma -- and refits otherwise."""
+		if iterative and self.x is not None and Sigma is None and self._Sigma is None:
+			self.fit_gp(x, y, iterative=True, extrapoint=True)
+			return
 		if self.x is not None:
 			self.x = torch.cat((self.x, x), dim=0)
 			self.y = torch.cat((self.y, y), dim=0)
@@ -283,7 +289,18 @@ class GaussianProcess(Estimator):
 		return None if a is None else _lib.like_input(a.reshape(-1, 1), self.x)
 
 	def fit_gp(self, x, y, Sigma=None, iterative=False, extrapoint=False):
-		"""gauss_procc.py:136-177 (the ``iterative`` branch of the reference is a stub and is ignored)."""
+		"""gauss_procc.py:136-177.  ``extrapoint=True``: x, y are only the points to add to the fitted data; otherwise they are all of
+		it.  ``iterative=True``: the rows beyond the fitted ones extend the resident factor (bordered Cholesky, stpy_potrf_append)
+		instead of refactoring -- taken only when the factor was built with the current noise level and kernel parameters, without
+		an explicit Sigma, in the same dtype; anything else (an unfitted GP included) is the ordinary fit on all the data."""
+		if extrapoint and self.x is not None:
+			x, xn = torch.cat((self.x, x), dim=0), x
+			y, yn = torch.cat((self.y, y), dim=0), y
+		else:
+			xn, yn = x[self.n:], y[self.n:]
+		if iterative and xn.shape[0] > 0 and self._can_append(x, Sigma):
+			if self._append(x, y, xn, yn):
+				return None
 		try:
 			self.n, self.d = list(x.size())
 		except Exception:
@@ -297,7 +314,7 @@ class GaussianProcess(Estimator):
 		# object that takes the prior branch instead of one that reports fitted=True with no factor behind it
 		self.fitted = False
 		self._L = self._winv = self._z = self._alpha_cache = None       # release the previous factor before allocating the next
-		self._Lr = self._winvr = None
+		self._Lr = self._winvr = self._Lbuf = None
 		L, winv, info = self._factor(self._xd, None, Sigma, defer_check=True)
 		z = self._forward_y(L, winv, self._yd)
 		# A = K^-1 y is part of the fitted state the reference leaves behind (gauss_procc.py:376): computed
@@ -313,6 +330,68 @@ class GaussianProcess(Estimator):
 		self._factor_key = self._hyper_key(self.kernel_object)
 		self.fitted = True
 		return None
+
+	def _can_append(self, x, Sigma):
+		"""The bordered update computes what a refit would: the factor exists and was built from the current s / kernel parameters
+		with the s^2 I noise, and the new points come in its dtype."""
+		return (self.fitted and self._L is not None and Sigma is None and self._Sigma is None
+				and getattr(self, "_factor_key", None) == self._hyper_key(self.kernel_object)
+				and (x.dtype if torch.is_tensor(x) and x.dtype in (torch.float32, torch.float64) else torch.float64) == self._xd.dtype
+				and x.shape[1] == self._xd.shape[1])
+
+	def _append(self, x, y, xn, yn):
+		"""Extend the resident factor by the rows xn (x, y: all the data afterwards).  The factor lives in a buffer of capacity cap >= the
+		padded order (``_L`` is its leading view, leading dimension cap): appends that fit are in place; a full buffer is replaced by one
+		with a tile of headroom, so single-point appends copy the factor at most once per 128 points.  Returns False (the caller refits)
+		when that allocation fails."""
+		lib = _lib.load()
+		dtype, dev = self._xd.dtype, self._xd.device
+		xd_new = _lib.to_device(xn, dtype)
+		yd_new = _lib.to_device(yn, dtype).reshape(-1).contiguous()
+		n0, k = self.n, xd_new.shape[0]
+		n1 = n0 + k
+		n1p = _tile_pad(n1)
+		buf = getattr(self, "_Lbuf", None)
+		buf = self._L if buf is None else buf
+		winv = self._winv
+		if n1p > buf.shape[0]:
+			n0p = self._L.shape[0]
+			cap = n1p + 128
+			try:
+				nbuf = torch.zeros((cap, cap), dtype=dtype, device=dev)
+				nwinv = torch.empty((int(lib.stpy_potrf_winv_elems(cap)),), dtype=dtype, device=dev)
+			except RuntimeError:
+				nbuf = nwinv = None
+				self.fitted = False
+				self._L = self._Lbuf = self._winv = self._z = self._alpha_cache = self._Lr = self._winvr = None
+				return False
+			nbuf[:n0p, :n0p].copy_(self._L)
+			nwinv[:int(lib.stpy_potrf_winv_elems(n0p))].copy_(winv[:int(lib.stpy_potrf_winv_elems(n0p))])
+			buf, winv = nbuf, nwinv
+			self._L = None
+		# the new rows of K + s^2 I straight into the factor's buffer: K(x_new, x_old) and the lower part of K(x_new, x_new)
+		self.kernel_object._kernel_into(self._xd, xd_new, buf[n0:n1, :n0])
+		self.kernel_object._kernel_into(xd_new, xd_new, buf[n0:n1, n0:n1], diag_add=float(self.s) ** 2, lower_only=True)
+		z = torch.zeros((n1p,), dtype=dtype, device=dev)
+		z[:n0] = self._z[:n0]
+		dt = _lib.dtype_code(dtype)
+		work = torch.empty((max(int(lib.stpy_potrf_append_workspace_bytes(dt, n0, k)), 1),), dtype=torch.uint8, device=dev)
+		info = torch.zeros((1,), dtype=torch.int32, device=dev)
+		rc = lib.stpy_potrf_append(dt, n0, k, _lib.ptr(buf), buf.stride(0), _lib.ptr(winv), winv.numel(), _lib.ptr(z), _lib.ptr(yd_new),
+								   _lib.ptr(work), work.numel(), _lib.ptr(info), _lib.stream_ptr())
+		# from here on the object describes the new data set, fitted only once the extended factor is known to be good
+		self.x, self.y, self.n = x, y, n1
+		self._xd = torch.cat((self._xd, xd_new), dim=0)
+		self._yd = torch.cat((self._yd, yd_new.reshape(-1, 1)), dim=0)
+		self.fitted = False
+		self._alpha_cache = self._Lr = self._winvr = None
+		self._L = self._Lbuf = self._winv = self._z = None
+		_lib.check(rc, "stpy_potrf_append")
+		self._check_info(info)
+		_lib.check_async("add_data_point: stpy_potrf_append")
+		self._Lbuf, self._L, self._winv, self._z = buf, buf[:n1p, :n1p], winv, z
+		self.fitted = True
+		return True
 
 	def _hyper_key(self, kernel):
 		"""What the resident factor was built from: the noise level and every stored kernel parameter, by value.

@@ -159,6 +159,28 @@ int stpy_potrf(int dtype, int64_t n, void* A, int64_t lda, void* winv, int64_t w
 	         potrf<float>(n, (float*)A, lda, (float*)winv, (float*)work, nb, info_dev, st, gf));
 }
 
+int64_t stpy_potrf_append_workspace_bytes(int dtype, int64_t n0, int64_t k)
+{
+	if (n0 <= 0 || k <= 0) return 0;
+	return potrf_append_workspace_bytes(dtype == STPY_F32 ? 4 : 8, n0, k);
+}
+
+int stpy_potrf_append(int dtype, int64_t n0, int64_t k, void* A, int64_t lda, void* winv, int64_t winv_elems, void* z, const void* y,
+                      void* work, int64_t work_bytes, int32_t* info_dev, void* stream)
+{
+	if (n0 <= 0) { set_error("stpy_potrf_append: n0=%lld (the resident factor must hold at least one row)", (long long)n0); return -2; }
+	if (k <= 0) { set_error("stpy_potrf_append: k=%lld new rows", (long long)k); return -3; }
+	if (!A || !winv || !work || !info_dev || (z && !y)) { set_error("stpy_potrf_append: null pointer"); return -4; }
+	const int64_t n1p = (n0 + k + IB - 1) / IB * IB;
+	if (lda < n1p) { set_error("stpy_potrf_append: lda=%lld below the padded order %lld", (long long)lda, (long long)n1p); return -5; }
+	WINV_CHECK("stpy_potrf_append", winv_elems, n1p);
+	WORK_CHECK("stpy_potrf_append", work_bytes, stpy_potrf_append_workspace_bytes(dtype, n0, k));
+	hipStream_t st = (hipStream_t)stream;
+	DISPATCH(dtype,
+	         potrf_append<double>(n0, k, (double*)A, lda, (double*)winv, (double*)z, (const double*)y, work, info_dev, st),
+	         potrf_append<float>(n0, k, (float*)A, lda, (float*)winv, (float*)z, (const float*)y, work, info_dev, st));
+}
+
 int64_t stpy_trsm_workspace_bytes(int dtype, int64_t m, int64_t n, int nb)
 {
 	if (m <= 0 || n <= 0) return 0;
@@ -457,6 +479,7 @@ void stpy_tune(int key, int value)
 	case 28: g_gram_fill = value; return;
 	case 30: g_gemm_sliver_tiles = value; return;
 	case 32: g_potrf_presplit = value; return;
+	case 34: g_append_mfma_above = value; return;
 	default: break;
 	}
 #if STPY_LAB
@@ -481,6 +504,7 @@ int stpy_tune_get(int key)
 	case 28: return g_gram_fill;
 	case 30: return g_gemm_sliver_tiles;
 	case 32: return g_potrf_presplit;
+	case 34: return g_append_mfma_above;
 	default: break;
 	}
 #if STPY_LAB

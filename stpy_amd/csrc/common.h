@@ -11,9 +11,10 @@ namespace stpy {
 constexpr int IB = 128;          // inner (diagonal) block of the factorisation / solves
 constexpr int POTRF_DEFAULT_NB = 1024, TRSM_DEFAULT_NB = 512;
 // ---- switches ---------------------------------------------------------------------------------------------------------
-// ROUTE switches (stpy_tune keys 5, 8, 9, 16, 17, 26, 28, 30; every build): which of the SHIPPED kernels serves a call where the library
+// ROUTE switches (stpy_tune keys 5, 8, 9, 16, 17, 26, 28, 30, 32, 34; every build): which of the SHIPPED kernels serves a call where the library
 // normally decides by size -- tests/ use them to reach every shipped path at small sizes.  Process-wide, read at launch time.
-extern int g_trsm_right_looking, g_gemm_k128, g_rff_tile, g_trsv_flow, g_trsm_strip, g_gemm_bf3, g_gram_fill, g_gemm_sliver_tiles, g_potrf_presplit;
+extern int g_trsm_right_looking, g_gemm_k128, g_rff_tile, g_trsv_flow, g_trsm_strip, g_gemm_bf3, g_gram_fill, g_gemm_sliver_tiles, g_potrf_presplit,
+           g_append_mfma_above;
 // EXPERIMENT knobs: compile-time constants in the product library (the measured defaults); variables behind stpy_tune only in
 // the lab build (make EXPERIMENTS=1 -> libstpy_hip_lab.so, used by tools/).  The kernels and code paths that only a non-default
 // value reaches are compiled under #if STPY_LAB, so the product library does not carry them.  Where each default comes from is
@@ -55,6 +56,14 @@ struct LookAhead {
 	// 64 bytes of device memory: ticket / published-count / error words of the one-launch vector solve (solve.hip)
 	void* trsv_sync = nullptr;
 };
+// layout of those 64 bytes: ticket / count are zeroed before every one-launch solve; `error` is STICKY (set when a hand-off wait
+// gives up, read and cleared by stpy_async_status).  Shared by stpy_trsv (solve.hip) and stpy_potrf_append (append.hip).
+struct TrsvSync { unsigned ticket, count, error, pad; };
+// the hand-off accesses of those solves: agent-scope relaxed atomics = write-through (sc1) vector stores / loads
+template <typename T>
+__device__ __forceinline__ T load_sc1(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <typename T>
+__device__ __forceinline__ void store_sc1(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 int lookahead_acquire(hipStream_t caller, LookAhead** out);
 
 // per-call behaviour flags of stpy_potrf / stpy_trsm_right_lt (include/stpy_hip.h: STPY_FLAG_*), passed down to the GEMM launcher
@@ -150,6 +159,9 @@ template <typename T>
 int combine_into(int64_t m, int64_t n, T* out, int64_t ldo, const T* src, int64_t lds, int combine, double diag_add, hipStream_t st);
 template <typename T>
 int predict_finish(int64_t m, T* mu, const T* sumsq, const T* kdiag, double scale, T* sigma, int clamp, hipStream_t st);
+template <typename T>
+int potrf_append(int64_t n0, int64_t k, T* A, int64_t lda, T* winv, T* z, const T* y, void* work, int32_t* info, hipStream_t st);
+int64_t potrf_append_workspace_bytes(size_t esz, int64_t n0, int64_t k);
 template <typename T>
 int trsv(int64_t n, const T* L, int64_t ldl, const T* winv, T* y, T* out, int trans, hipStream_t st);
 int trsv_async_status(hipStream_t st, int* status);      // solve.hip: sticky device error word of the one-launch vector solves on `st`

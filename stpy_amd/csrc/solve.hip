@@ -500,13 +500,8 @@ void trsv_bwd_step(const T* __restrict__ L, int64_t ldl, const T* __restrict__ W
 // ------------------------------------------------------------------------------------------
 // ticket / count are zeroed before every launch; `error` is STICKY (set when a hand-off wait gives up, read and cleared by
 // stpy_async_status): a timed-out solve also poisons its output with NaN, so the failure shows in every result derived from it
-struct TrsvSync { unsigned ticket, count, error, pad; };
+// (TrsvSync, load_sc1 / store_sc1: common.h -- the multi-right-hand-side solve of append.hip shares them)
 int g_trsv_flow = 1;           // stpy_tune key 16: 0 = always the chain of step kernels
-
-template <typename T>
-__device__ __forceinline__ T load_sc1(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T>
-__device__ __forceinline__ void store_sc1(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 template <typename T, bool BACK>
 __global__ __launch_bounds__(256, 1)

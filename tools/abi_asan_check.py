@@ -16,7 +16,7 @@ import textwrap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "stpy_amd", "csrc")
-SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce", "grad"]
+SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce", "grad", "append"]
 
 CHILD = r'''
 import ctypes, sys
@@ -110,6 +110,15 @@ zero(lib.stpy_gram_grad(0, 0, N, 0, 4, N, 4, 4, 2, N, N, 1.0, 0.0, N, N, N, 0, N
 neg(lib.stpy_trsm_ln_factor(0, 200, P, 200, P, 1 << 20, P, 200, P, N), "trsm_ln_factor n not tile-aligned")
 neg(lib.stpy_trsm_right_ln(0, 8, 256, N, 256, P, 1 << 20, P, 256, 0, 0, N, 0, N), "trsm_right_ln null L")
 neg(lib.stpy_trsm_right_ln(0, 8, 256, P, 256, P, 10, P, 256, 0, 0, N, 0, N), "trsm_right_ln winv too small")
+neg(lib.stpy_potrf_append(0, 0, 4, P, 256, P, 1 << 20, P, P, P, 1 << 30, P, N), "potrf_append n0 = 0")
+neg(lib.stpy_potrf_append(0, 100, 0, P, 256, P, 1 << 20, P, P, P, 1 << 30, P, N), "potrf_append k = 0")
+neg(lib.stpy_potrf_append(0, 100, 4, N, 256, P, 1 << 20, P, P, P, 1 << 30, P, N), "potrf_append null A")
+neg(lib.stpy_potrf_append(0, 100, 4, P, 256, P, 1 << 20, P, N, P, 1 << 30, P, N), "potrf_append z without y")
+neg(lib.stpy_potrf_append(0, 100, 40, P, 128, P, 1 << 20, P, P, P, 1 << 30, P, N), "potrf_append lda < n1p")
+assert lib.stpy_potrf_append(0, 100, 40, P, 256, P, 128 * 128, P, P, P, 1 << 30, P, N) == -21, "potrf_append winv too small"
+assert lib.stpy_potrf_append(0, 100, 40, P, 256, P, 1 << 20, P, P, P, 10, P, N) == -20, "potrf_append workspace too small"
+neg(lib.stpy_potrf_append(7, 100, 4, P, 256, P, 1 << 20, P, P, P, 1 << 30, P, N), "potrf_append unknown dtype")
+zero(lib.stpy_potrf_append_workspace_bytes(0, 0, 4), "potrf_append workspace query, n0 = 0")
 # ---- RFF
 assert lib.stpy_rff_workspace_bytes(1, 262144, 64, 32768) > 0 and lib.stpy_rff_workspace_bytes(0, 100, 5, 64) == 0
 neg(lib.stpy_rff_embed(1, N, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 0, N, 0, N), "rff null x")
