@@ -1,5 +1,7 @@
 """
-ctypes binding of libstpy_hip.so (include/stpy_hip.h).
+ctypes binding of libstpy_hip.so (include/stpy_hip.h), and the typed wrappers through which the rest of the package launches:
+this is the one module that knows the calling convention (dtype codes, leading dimensions, workspace / winv sizing, the
+status word, the stream).
 
 The shared library is built in-tree by ``__graft_entry__.build()`` / ``make -C stpy_amd/csrc``.
 There is no CPU fallback: if the library is missing, or no ROCm device is visible, the product
@@ -136,9 +138,9 @@ def ptr(t):
 
 
 def ld(t):
-	"""Leading dimension (elements) of a row-major 2-D tensor.  A one-row tensor reports whatever stride(0) its history left behind
-	(``x.T.contiguous()`` of an (n, 1) tensor keeps stride 1): there the row length is the only valid answer."""
-	return t.stride(0) if t.shape[0] > 1 else max(int(t.shape[1]), 1)
+	"""Leading dimension (elements) of a row-major 2-D tensor: stride(0).  A one-row tensor may report a stride(0) below its row length
+	(``x.T.contiguous()`` of an (n, 1) tensor keeps stride 1): it gets the row length instead."""
+	return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), int(t.shape[1]), 1)
 
 
 def to_device(t, dtype=None):
@@ -161,3 +163,233 @@ def like_input(result, ref):
 	if torch.is_tensor(ref) and ref.is_cuda:
 		return result
 	return result.cpu()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Typed wrappers, one per launch entry point the package uses.  Each takes torch tensors; derives the dtype code, the dimensions,
+# the leading dimensions and the stream (read at call time: the block-cyclic code launches from side streams); allocates the
+# workspace the matching query asks for, alive for the call only unless the caller passes a buffer it keeps; and checks the return
+# code under the entry point's name.  Arguments that select a kernel route (nb, flags, workspace, mode, lower_only) are the
+# caller's.  Nothing here waits for the device.
+
+def _launch(name, *args):
+	check(getattr(load(), name)(*args, stream_ptr()), name)
+
+
+def _work(nbytes, like):
+	return torch.empty((int(nbytes),), dtype=torch.uint8, device=like.device)
+
+
+def _ncols(x, cols):
+	"""Coordinates a kernel reads: the ones listed in the device int32 array ``cols``, else every column of x."""
+	return x.shape[1] if cols is None else cols.numel()
+
+
+def gram_workspace(n, q, d, like):
+	"""Scratch of stpy_gram for n x q points of d coordinates (one buffer can serve several launches)."""
+	return _work(load().stpy_gram_workspace_bytes(dtype_code(like.dtype), n, q, d), like)
+
+
+def gram(kind, a, b, out, inv_ls, cols=None, kappa=1.0, offset=0.0, diag_add=0.0, lower_only=False, combine=OUT_SET, work=None):
+	"""out[j, i] (combine)= k(a_i, b_j) + diag_add [i == j]; out: (|b|, |a|), may be a view."""
+	n, q, d = a.shape[0], b.shape[0], _ncols(a, cols)
+	work = gram_workspace(n, q, d, out) if work is None else work
+	_launch("stpy_gram", kind, dtype_code(out.dtype), ptr(a), n, ld(a), ptr(b), q, ld(b), d, ptr(cols), ptr(inv_ls), kappa, offset, diag_add,
+			int(lower_only), combine, ptr(out), ld(out), ptr(work), work.numel())
+
+
+def gram_diag(kind, x, out, inv_ls, cols=None, kappa=1.0, offset=0.0, combine=OUT_SET, d=None):
+	"""out[i] (combine)= k(x_i, x_i).  d: coordinates read (default as gram; 0 for a kernel whose diagonal does not depend on x)."""
+	_launch("stpy_gram_diag", kind, dtype_code(out.dtype), ptr(x), x.shape[0], ld(x), _ncols(x, cols) if d is None else d, ptr(cols), ptr(inv_ls),
+			kappa, offset, combine, ptr(out))
+
+
+def gram_grad(kind, x, xt, G, inv_ls, cols=None, kappa=1.0, offset=0.0, alpha=None, u=None, Wt=None, v=None, combine=OUT_SET, H=None):
+	"""G[t] (combine)= d/dxt_t sum_i (u_t alpha_i + v_t Wt[t, i]) k(xt_t, x_i); with H also the second derivatives."""
+	m, n, d = xt.shape[0], x.shape[0], _ncols(x, cols)
+	order = 1 if H is None else 2
+	work = _work(load().stpy_gram_grad_workspace_bytes(dtype_code(G.dtype), m, n, d, order), G)
+	_launch("stpy_gram_grad", kind, dtype_code(G.dtype), ptr(x), n, ld(x), ptr(xt), m, ld(xt), d, ptr(cols), ptr(inv_ls), float(kappa), float(offset),
+			ptr(alpha), ptr(u), ptr(Wt), ld(Wt) if Wt is not None else 0, ptr(v), order, combine, ptr(G), ld(G), ptr(H), ptr(work), work.numel())
+
+
+def combine(out, src, op=OUT_SET, diag_add=0.0):
+	"""out (op)= src elementwise, then + diag_add on the diagonal; src may be out."""
+	_launch("stpy_combine", dtype_code(out.dtype), out.shape[0], out.shape[1], ptr(out), ld(out), ptr(src), ld(src), op, diag_add)
+
+
+def gemm_nt(A, B, C, mode=0, lower_only=False):
+	"""C (mode 0: =, 1: -=, 2: +=) A B^T."""
+	_launch("stpy_gemm_nt", dtype_code(C.dtype), A.shape[0], B.shape[0], A.shape[1], ptr(A), ld(A), ptr(B), ld(B), ptr(C), ld(C), mode, int(lower_only))
+
+
+def gemm_nt_splitk_passes(A, B):
+	"""K passes the library recommends for A B^T (1: gemm_nt)."""
+	return int(load().stpy_gemm_nt_splitk_passes(A.shape[0], B.shape[0], A.shape[1]))
+
+
+def gemm_nt_splitk(A, B, C, mode, passes, work):
+	"""gemm_nt in ``passes`` K pieces summed in a fixed order; work: at least passes * |A| * |B| elements."""
+	_launch("stpy_gemm_nt_splitk", dtype_code(C.dtype), A.shape[0], B.shape[0], A.shape[1], ptr(A), ld(A), ptr(B), ld(B), ptr(C), ld(C), mode,
+			passes, ptr(work), work.numel() * work.element_size())
+
+
+def gemm_nt_bc(A, B, C, mode, bc):
+	"""gemm_nt on a window of a block-cyclic local matrix; bc = (nb_dist, pr, pc, myr, myc, i0, j0)."""
+	_launch("stpy_gemm_nt_bc", dtype_code(C.dtype), A.shape[0], B.shape[0], A.shape[1], ptr(A), ld(A), ptr(B), ld(B), ptr(C), ld(C), mode,
+			*[int(v) for v in bc])
+
+
+def syrk(A, C, mode=0):
+	"""C (mode) A A^T on the lower tiles, with a workspace where the library has a use for one."""
+	n, k = A.shape
+	wb = int(load().stpy_syrk_workspace_bytes(dtype_code(C.dtype), n, k))
+	work = _work(wb, C) if wb > 0 else None
+	_launch("stpy_syrk", dtype_code(C.dtype), n, k, ptr(A), ld(A), ptr(C), ld(C), mode, ptr(work), wb)
+
+
+def potrf_winv_elems(n):
+	return int(load().stpy_potrf_winv_elems(n))
+
+
+def potrf(A, nb=0, flags=0):
+	"""In-place Cholesky of the square view A.  Returns (winv, info): the inverse diagonal blocks and the device status word (first
+	failing pivot, 1-based), unread -- the caller decides when to wait for it."""
+	n = A.shape[0]
+	winv = torch.empty((potrf_winv_elems(n),), dtype=A.dtype, device=A.device)
+	work = _work(load().stpy_potrf_workspace_bytes(dtype_code(A.dtype), n, nb), A)
+	info = torch.zeros((1,), dtype=torch.int32, device=A.device)
+	_launch("stpy_potrf", dtype_code(A.dtype), n, ptr(A), ld(A), ptr(winv), winv.numel(), ptr(work), work.numel(), nb, flags, ptr(info))
+	return winv, info
+
+
+def potrf_append(A, n0, winv, z, y):
+	"""Extends the factor in rows [0, n0) of A by len(y) rows, z from L^-1 y_old to L^-1 y (layout: stpy_potrf_append in the header).
+	Returns the unread status word, as potrf."""
+	k = y.shape[0]
+	work = _work(max(int(load().stpy_potrf_append_workspace_bytes(dtype_code(A.dtype), n0, k)), 1), A)
+	info = torch.zeros((1,), dtype=torch.int32, device=A.device)
+	_launch("stpy_potrf_append", dtype_code(A.dtype), n0, k, ptr(A), ld(A), ptr(winv), winv.numel(), ptr(z), ptr(y), ptr(work), work.numel(), ptr(info))
+	return info
+
+
+def potri(L, winv, n=None, work=None):
+	"""(L L^T)^-1, full symmetric: the leading n x n block (default: all) of a new matrix of L's order.  work: scratch of that size,
+	allocated here unless the caller keeps one."""
+	N = L.shape[0]
+	Kinv = torch.empty((N, N), dtype=L.dtype, device=L.device)
+	work = torch.empty((N, N), dtype=L.dtype, device=L.device) if work is None else work
+	_launch("stpy_potri", dtype_code(L.dtype), N, ptr(L), ld(L), ptr(winv), winv.numel(), ptr(Kinv), ld(Kinv), ptr(work),
+			work.numel() * work.element_size())
+	Kinv = Kinv[:n, :n]
+	symmetrize_lower(Kinv)
+	return Kinv
+
+
+def _trsm(name, B, L, winv, nb, flags, workspace):
+	m, n = B.shape
+	work = _work(load().stpy_trsm_workspace_bytes(dtype_code(B.dtype), m, n, nb), B) if workspace else None
+	_launch(name, dtype_code(B.dtype), m, n, ptr(L), ld(L), ptr(winv), winv.numel(), ptr(B), ld(B), nb, flags, ptr(work), 0 if work is None else work.numel())
+
+
+def trsm_right_lt(B, L, winv, nb=0, flags=0, workspace=False):
+	"""B <- B L^-T in place.  ``workspace`` selects the algorithm: with one, large solves may run left-looking with K passes."""
+	_trsm("stpy_trsm_right_lt", B, L, winv, nb, flags, workspace)
+
+
+def trsm_right_ln(B, Lr, winvr, nb=0, flags=0, workspace=False):
+	"""B <- B L^-1 in place, from the reversed factor of trsm_ln_factor."""
+	_trsm("stpy_trsm_right_ln", B, Lr, winvr, nb, flags, workspace)
+
+
+def trsm_ln_factor(L, winv):
+	"""(Lr, winvr): the reversed factor J L^T J and its inverse diagonal blocks."""
+	Lr, winvr = torch.empty_like(L), torch.empty_like(winv)
+	_launch("stpy_trsm_ln_factor", dtype_code(L.dtype), L.shape[0], ptr(L), ld(L), ptr(winv), winv.numel(), ptr(Lr), ld(Lr), ptr(winvr))
+	return Lr, winvr
+
+
+def trsv(L, winv, rhs, trans=0):
+	"""L^-1 rhs (trans = 0) or L^-T rhs (trans = 1), a vector of L's order; rhs, zero-padded to that order, is left as it is."""
+	n = L.shape[0]
+	rhs = rhs.reshape(-1)
+	if rhs.numel() == n:
+		y = rhs.clone()
+	else:
+		y = torch.zeros((n,), dtype=L.dtype, device=L.device)
+		y[:rhs.numel()] = rhs
+	out = torch.empty_like(y)
+	_launch("stpy_trsv", dtype_code(L.dtype), n, ptr(L), ld(L), ptr(winv), winv.numel(), ptr(y), ptr(out), trans)          # (y: scratch)
+	return out
+
+
+def predict(X, z, mu=None, sigma=None, kdiag=None, clamp=0):
+	"""mu[i] = <X_i, z>, sigma[i] = sqrt(kdiag[i] - <X_i, X_i>) (clamp 1: clamped at 0; 2: sigma[i] = <X_i, X_i>); either may be None."""
+	_launch("stpy_predict", dtype_code(X.dtype), X.shape[0], X.shape[1], ptr(X), ld(X), ptr(z), ptr(kdiag), ptr(mu), ptr(sigma), clamp)
+
+
+def predict_finish(mu=None, sumsq=None, kdiag=None, scale=1.0, sigma=None, clamp=0):
+	"""mu *= scale in place, sigma = sqrt(kdiag - scale * sumsq); either may be None."""
+	t = mu if mu is not None else sigma
+	_launch("stpy_predict_finish", dtype_code(t.dtype), t.shape[0], ptr(mu), ptr(sumsq), ptr(kdiag), scale, ptr(sigma), clamp)
+
+
+def logdet_quad(L, z=None):
+	"""[sum_i log L_ii, z^T z] (z None: 0), a 2-element device tensor."""
+	out2 = torch.empty((2,), dtype=L.dtype, device=L.device)
+	_launch("stpy_logdet_quad", dtype_code(L.dtype), L.shape[0], ptr(L), ld(L), ptr(z), ptr(out2))
+	return out2
+
+
+def trace_dot(A=None, u=None, v=None):
+	"""[tr(A), <u, v>] (A or u None: 0) in a fixed summation order, a 2-element device tensor."""
+	t = A if A is not None else u
+	out2 = torch.empty((2,), dtype=t.dtype, device=t.device)
+	_launch("stpy_trace_dot", dtype_code(t.dtype), t.shape[0], ptr(A), ld(A) if A is not None else 0, ptr(u), ptr(v), ptr(out2))
+	return out2
+
+
+def tril(A):
+	_launch("stpy_tril", dtype_code(A.dtype), A.shape[0], ptr(A), ld(A))
+
+
+def symmetrize_lower(A):
+	_launch("stpy_symmetrize_lower", dtype_code(A.dtype), A.shape[0], ptr(A), ld(A))
+
+
+def scaled_points_t(x, inv_ls, cols=None):
+	"""[Xs | 1]^T, (d + 1, n): the rows of x[:, cols] * inv_ls as columns, then a row of ones."""
+	n, d = x.shape[0], _ncols(x, cols)
+	out = torch.empty((d + 1, n), dtype=x.dtype, device=x.device)
+	_launch("stpy_scaled_points_t", dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), ptr(out), ld(out), 1)
+	return out
+
+
+def lml_weight(kind, x, inv_ls, kappa, weight, alpha, Kinv, H, cols=None):
+	"""H = (weight Kinv - alpha alpha^T) o F, F the lengthscale-derivative factor of one kernel term; H may be Kinv."""
+	n, d = x.shape[0], _ncols(x, cols)
+	work = gram_workspace(n, n, d, x)
+	_launch("stpy_lml_weight", kind, dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), kappa, weight, ptr(alpha), ptr(Kinv), ld(Kinv),
+			ptr(H), ld(H), ptr(work), work.numel())
+
+
+def lml_grad_reduce(x, inv_ls, P, pidx, acc, cols=None):
+	_launch("stpy_lml_grad_reduce", dtype_code(x.dtype), ptr(x), x.shape[0], ld(x), _ncols(x, cols), ptr(cols), ptr(inv_ls), ptr(P), ld(P), ptr(pidx),
+			ptr(acc))
+
+
+def lml_grad_cov_reduce(x, z, P, out, cols=None):
+	_launch("stpy_lml_grad_cov_reduce", dtype_code(x.dtype), ptr(x), x.shape[0], ld(x), _ncols(x, cols), ptr(cols), ptr(z), ld(z), z.shape[1], ptr(P),
+			ld(P), ptr(out))
+
+
+def rff_embed(x, W, m, scale, bias=None, feat_scale=None, transposed=False, workspace=False):
+	"""Random-feature embedding of the rows of x by the first m rows of W: (n, m), or (m, n) when ``transposed``.  ``workspace``
+	passes the library's, which moves the large fp32 d = 64 shapes to the bf16 matrix cores."""
+	n, d = x.shape
+	out = torch.empty((m, n) if transposed else (n, m), dtype=x.dtype, device=x.device)
+	wb = int(load().stpy_rff_workspace_bytes(dtype_code(x.dtype), n, d, m)) if workspace else 0
+	work = _work(wb, x) if wb > 0 else None
+	_launch("stpy_rff_embed", dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(W), ld(W), m, ptr(bias), ptr(feat_scale), scale, ptr(out), ld(out),
+			int(transposed), ptr(work), wb)
+	return out

@@ -206,28 +206,23 @@ class GaussianProcess(Estimator):
 	@staticmethod
 	def _add_noise_gram(K, Sigma):
 		"""K += Sigma^T Sigma = K - (-Sigma^T)(Sigma^T)^T: one stpy_gemm_nt in subtract mode."""
-		lib = _lib.load()
 		St = _lib.to_device(Sigma, K.dtype).t().contiguous()
-		nSt = -St
-		n = K.shape[0]
-		_lib.check(lib.stpy_gemm_nt(_lib.dtype_code(K.dtype), n, n, St.shape[1], _lib.ptr(nSt), _lib.ld(nSt), _lib.ptr(St), _lib.ld(St),
-									_lib.ptr(K), _lib.ld(K), 1, 0, _lib.stream_ptr()), "stpy_gemm_nt")
+		_lib.gemm_nt(-St, St, K, 1)
 
 	@staticmethod
-	def _check_info(info):
-		"""The one synchronisation of a fit: the factorisation's status word (first failing pivot, 1-based; 0 = fine)."""
+	def _check_info(info, what="stpy_potrf: the leading minor of order %d of K + s^2 I is not positive definite"):
+		"""The one synchronisation of a fit: the factorisation's status word (first failing pivot, 1-based; 0 = fine).  ``what``: the
+		message of the LinAlgError raised for a failing pivot, with a %d for its order."""
 		bad = int(info.item())
 		if bad != 0:
-			raise torch.linalg.LinAlgError("stpy_potrf: the leading minor of order %d of K + s^2 I is not positive definite" % bad)
+			raise torch.linalg.LinAlgError(what % bad)
 
 	def _factor(self, xd, kwargs=None, Sigma=None, defer_check=False):
 		"""K_theta = k(x,x) + s^2 I (or + Sigma^T Sigma) -> in-place Cholesky.  Returns (L, winv); with ``defer_check`` also the
 		device status word, unread -- the caller enqueues what follows the factorisation first and then calls ``_check_info``,
 		so the device does not idle through the host round trip."""
-		lib = _lib.load()
 		n0 = xd.shape[0]
 		n = _tile_pad(n0)
-		dt = _lib.dtype_code(xd.dtype)
 		# The matrix is held at the next multiple of the 128-tile, bordered by an identity block:
 		# chol([[K, 0], [0, I]]) = [[L, 0], [0, I]], so every product of the factorisation and of the
 		# solves below runs on the tile-aligned kernels whatever N is (a ragged N = 32 700 cost 30 %).
@@ -245,41 +240,17 @@ class GaussianProcess(Estimator):
 			self.kernel_object._kernel_into(xd, xd, K, kwargs)
 			self._add_noise_gram(K, Sigma)
 		K = Kp
-		winv = torch.empty((int(lib.stpy_potrf_winv_elems(n)),), dtype=xd.dtype, device=xd.device)
-		work = torch.empty((int(lib.stpy_potrf_workspace_bytes(dt, n, self.nb)),), dtype=torch.uint8, device=xd.device)
-		info = torch.zeros((1,), dtype=torch.int32, device=xd.device)
-		rc = lib.stpy_potrf(dt, n, _lib.ptr(K), _lib.ld(K), _lib.ptr(winv), winv.numel(), _lib.ptr(work), work.numel() * work.element_size(), self.nb, 0, _lib.ptr(info), _lib.stream_ptr())
-		_lib.check(rc, "stpy_potrf")
-		del work
+		winv, info = _lib.potrf(K, self.nb)
 		if defer_check:
 			return K, winv, info
 		self._check_info(info)
 		return K, winv
 
-	def _forward_y(self, L, winv, yd):
-		"""z = L^-1 y (length = the padded order of L; the padding of y is zero)."""
-		lib = _lib.load()
-		scratch = torch.zeros((L.shape[0],), dtype=L.dtype, device=L.device)
-		scratch[:yd.numel()] = yd.reshape(-1)
-		z = torch.empty_like(scratch)
-		_lib.check(lib.stpy_trsv(_lib.dtype_code(L.dtype), L.shape[0], _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(scratch), _lib.ptr(z), 0,
-								 _lib.stream_ptr()), "stpy_trsv")
-		return z
-
-	def _backward_z(self, L, winv, z):
-		"""alpha = L^-T z."""
-		lib = _lib.load()
-		scratch = z.clone()
-		alpha = torch.empty_like(scratch)
-		_lib.check(lib.stpy_trsv(_lib.dtype_code(L.dtype), L.shape[0], _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(scratch), _lib.ptr(alpha), 1,
-								 _lib.stream_ptr()), "stpy_trsv")
-		return alpha
-
 	@property
 	def _alpha(self):
 		"""K^-1 y = L^-T z on the device (filled by fit_gp)."""
 		if self._alpha_cache is None and self.fitted:
-			self._alpha_cache = self._backward_z(self._L, self._winv, self._z)[:self.n]
+			self._alpha_cache = _lib.trsv(self._L, self._winv, self._z, trans=1)[:self.n]
 		return self._alpha_cache
 
 	@property
@@ -316,10 +287,10 @@ class GaussianProcess(Estimator):
 		self._L = self._winv = self._z = self._alpha_cache = None       # release the previous factor before allocating the next
 		self._Lr = self._winvr = self._Lbuf = None
 		L, winv, info = self._factor(self._xd, None, Sigma, defer_check=True)
-		z = self._forward_y(L, winv, self._yd)
+		z = _lib.trsv(L, winv, self._yd)
 		# A = K^-1 y is part of the fitted state the reference leaves behind (gauss_procc.py:376): computed
 		# eagerly even though mean_std itself only needs z
-		alpha = self._backward_z(L, winv, z)[:self.n]
+		alpha = _lib.trsv(L, winv, z, trans=1)[:self.n]
 		# the two vector solves are already queued behind the factorisation when the host reads its status (on a matrix that is
 		# not positive definite they ran on garbage and are dropped with the exception: the object stays unfitted)
 		self._check_info(info)
@@ -344,7 +315,6 @@ class GaussianProcess(Estimator):
 		padded order (``_L`` is its leading view, leading dimension cap): appends that fit are in place; a full buffer is replaced by one
 		with a tile of headroom, so single-point appends copy the factor at most once per 128 points.  Returns False (the caller refits)
 		when that allocation fails."""
-		lib = _lib.load()
 		dtype, dev = self._xd.dtype, self._xd.device
 		xd_new = _lib.to_device(xn, dtype)
 		yd_new = _lib.to_device(yn, dtype).reshape(-1).contiguous()
@@ -359,14 +329,14 @@ class GaussianProcess(Estimator):
 			cap = n1p + 128
 			try:
 				nbuf = torch.zeros((cap, cap), dtype=dtype, device=dev)
-				nwinv = torch.empty((int(lib.stpy_potrf_winv_elems(cap)),), dtype=dtype, device=dev)
+				nwinv = torch.empty((_lib.potrf_winv_elems(cap),), dtype=dtype, device=dev)
 			except RuntimeError:
 				nbuf = nwinv = None
 				self.fitted = False
 				self._L = self._Lbuf = self._winv = self._z = self._alpha_cache = self._Lr = self._winvr = None
 				return False
 			nbuf[:n0p, :n0p].copy_(self._L)
-			nwinv[:int(lib.stpy_potrf_winv_elems(n0p))].copy_(winv[:int(lib.stpy_potrf_winv_elems(n0p))])
+			nwinv[:_lib.potrf_winv_elems(n0p)].copy_(winv[:_lib.potrf_winv_elems(n0p)])
 			buf, winv = nbuf, nwinv
 			self._L = None
 		# the new rows of K + s^2 I straight into the factor's buffer: K(x_new, x_old) and the lower part of K(x_new, x_new)
@@ -374,19 +344,15 @@ class GaussianProcess(Estimator):
 		self.kernel_object._kernel_into(xd_new, xd_new, buf[n0:n1, n0:n1], diag_add=float(self.s) ** 2, lower_only=True)
 		z = torch.zeros((n1p,), dtype=dtype, device=dev)
 		z[:n0] = self._z[:n0]
-		dt = _lib.dtype_code(dtype)
-		work = torch.empty((max(int(lib.stpy_potrf_append_workspace_bytes(dt, n0, k)), 1),), dtype=torch.uint8, device=dev)
-		info = torch.zeros((1,), dtype=torch.int32, device=dev)
-		rc = lib.stpy_potrf_append(dt, n0, k, _lib.ptr(buf), buf.stride(0), _lib.ptr(winv), winv.numel(), _lib.ptr(z), _lib.ptr(yd_new),
-								   _lib.ptr(work), work.numel(), _lib.ptr(info), _lib.stream_ptr())
-		# from here on the object describes the new data set, fitted only once the extended factor is known to be good
+		# from here on the object describes the new data set, fitted only once the extended factor is known to be good (the rows just
+		# written into the buffer overwrote the identity padding of the old factor)
 		self.x, self.y, self.n = x, y, n1
 		self._xd = torch.cat((self._xd, xd_new), dim=0)
 		self._yd = torch.cat((self._yd, yd_new.reshape(-1, 1)), dim=0)
 		self.fitted = False
 		self._alpha_cache = self._Lr = self._winvr = None
 		self._L = self._Lbuf = self._winv = self._z = None
-		_lib.check(rc, "stpy_potrf_append")
+		info = _lib.potrf_append(buf, n0, winv, z, yd_new)
 		self._check_info(info)
 		_lib.check_async("add_data_point: stpy_potrf_append")
 		self._Lbuf, self._L, self._winv, self._z = buf, buf[:n1p, :n1p], winv, z
@@ -438,34 +404,23 @@ class GaussianProcess(Estimator):
 		sqrt(alpha^T y - s^2 alpha^T alpha): no n x n matrix is formed."""
 		if not self.fitted:
 			return None
-		lib = _lib.load()
 		a = self._alpha.reshape(-1).contiguous()
-
-		def dot(u, v):          # <u, v> in the fixed-order reduction kernel, read back as a host scalar
-			o = torch.empty((2,), dtype=u.dtype, device=u.device)
-			_lib.check(lib.stpy_trace_dot(_lib.dtype_code(u.dtype), u.shape[0], None, 0, _lib.ptr(u), _lib.ptr(v), _lib.ptr(o), _lib.stream_ptr()), "stpy_trace_dot")
-			return float(o[1].item())
 		if self._Sigma is None:
-			noise = float(self.s) ** 2 * dot(a, a)
+			noise = float(self.s) ** 2 * float(_lib.trace_dot(u=a, v=a)[1].item())
 		else:                                   # general noise matrix: alpha^T Sigma^T Sigma alpha = |Sigma alpha|^2
 			Sd = _lib.to_device(self._Sigma, a.dtype).contiguous()
 			v = torch.empty((1, Sd.shape[0]), dtype=a.dtype, device=a.device)
-			_lib.check(lib.stpy_gemm_nt(_lib.dtype_code(a.dtype), 1, Sd.shape[0], Sd.shape[1], _lib.ptr(a), a.shape[0], _lib.ptr(Sd), _lib.ld(Sd),
-										_lib.ptr(v), _lib.ld(v), 0, 0, _lib.stream_ptr()), "stpy_gemm_nt")
+			_lib.gemm_nt(a.reshape(1, -1), Sd, v)
 			v = v.reshape(-1)
-			noise = dot(v, v)
-		val = dot(a, self._yd.reshape(-1).contiguous()) - noise
+			noise = float(_lib.trace_dot(u=v, v=v)[1].item())
+		val = float(_lib.trace_dot(u=a, v=self._yd.reshape(-1).contiguous())[1].item()) - noise
 		return _lib.like_input(torch.full((1, 1), math.sqrt(val) if val >= 0 else float("nan"), dtype=a.dtype), self.x)
 
 	def beta(self, delta=1e-3, norm=1):
 		"""gauss_procc.py:186-196: s * norm + sqrt(2 log(1/delta + log(det K / s^n))), K = k(x,x) + s^2 I.
 		log det K comes from the factor (2 sum log L_ii), so nothing overflows at sizes where det K would."""
-		lib = _lib.load()
 		L = self._L
-		out2 = torch.empty((2,), dtype=L.dtype, device=L.device)
-		_lib.check(lib.stpy_logdet_quad(_lib.dtype_code(L.dtype), L.shape[0], _lib.ptr(L), _lib.ld(L), None, _lib.ptr(out2),
-										_lib.stream_ptr()), "stpy_logdet_quad")
-		log_ratio = 2.0 * float(out2[0].item()) - self.n * math.log(float(self.s))          # host scalars from here on
+		log_ratio = 2.0 * float(_lib.logdet_quad(L)[0].item()) - self.n * math.log(float(self.s))          # host scalars from here on
 		arg = 1.0 / delta + log_ratio
 		val = float(self.s) * norm + (math.sqrt(2.0 * math.log(arg)) if arg >= 1.0 else float("nan"))
 		return _lib.like_input(torch.full((), val, dtype=L.dtype), self.x)
@@ -502,7 +457,6 @@ class GaussianProcess(Estimator):
 
 	def mean_std_sub(self, xtest, full=False, reuse=False):
 		"""gauss_procc.py:336-401 (squared loss)."""
-		lib = _lib.load()
 		ko = self.kernel_object
 		if not self.fitted:
 			xt = _lib.to_device(xtest)
@@ -514,8 +468,7 @@ class GaussianProcess(Estimator):
 				kd = torch.empty((xt.shape[0],), dtype=xt.dtype, device=xt.device)
 				ko._diag_into(xt, kd)
 				sd = torch.empty_like(kd)           # sqrt(diag K** - 0): the prediction epilogue with no data term
-				_lib.check(lib.stpy_predict_finish(_lib.dtype_code(xt.dtype), xt.shape[0], None, _lib.ptr(torch.zeros_like(kd)), _lib.ptr(kd), 0.0,
-												   _lib.ptr(sd), 0, _lib.stream_ptr()), "stpy_predict_finish")
+				_lib.predict_finish(sumsq=torch.zeros_like(kd), kdiag=kd, scale=0.0, sigma=sd)
 				yvar = sd.reshape(-1, 1)
 			zero = torch.zeros((xt.shape[0], 1), dtype=xt.dtype, device=xt.device)
 			return (_lib.like_input(zero, xtest), _lib.like_input(yvar, xtest))
@@ -525,25 +478,19 @@ class GaussianProcess(Estimator):
 		if not full:
 			mu, sigma, _ = self._predict(xt)
 			return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(sigma.reshape(-1, 1), xtest))
-		m, n = xt.shape[0], self._L.shape[0]
-		dt = _lib.dtype_code(xd.dtype)
-		st = _lib.stream_ptr
-		X = self._solve_kstar(xt)
+		m = xt.shape[0]
+		X = self._solve_kstar(xt)[:m]
 		mu = torch.empty((m,), dtype=xd.dtype, device=xd.device)
-		_lib.check(lib.stpy_predict(dt, m, n, _lib.ptr(X), _lib.ld(X), _lib.ptr(self._z), None, _lib.ptr(mu),
-									None, 0, st()), "stpy_predict")
+		_lib.predict(X, self._z, mu)
 		cov = torch.empty((m, m), dtype=xd.dtype, device=xd.device)
 		ko._kernel_into(xt, xt, cov)                                    # K**                      :343
-		_lib.check(lib.stpy_gemm_nt(dt, m, m, n, _lib.ptr(X), _lib.ld(X), _lib.ptr(X), _lib.ld(X), _lib.ptr(cov),
-									_lib.ld(cov), 1, 0, st()), "stpy_gemm_nt")                    # K** - X X^T  :396-399
+		_lib.gemm_nt(X, X, cov, 1)                                      # K** - X X^T  :396-399
 		return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(cov, xtest))
 
 	def _solve_kstar(self, xt):
 		"""X = K* L^-T (tile-padded: (mp, npad), zero rows past m and zero columns past n)."""
-		lib = _lib.load()
 		xd = self._xd
 		m, n0, n = xt.shape[0], self.n, self._L.shape[0]                # n: order of the (tile-padded) factor
-		dt = _lib.dtype_code(xd.dtype)
 		mp = _tile_pad(m)                                               # rows of K* padded to the tile as well (zero rows)
 		X = torch.empty((mp, n), dtype=xd.dtype, device=xd.device)
 		self.kernel_object._kernel_into(xd, xt, X[:m, :n0])             # K* = k(x, xtest): (M, N)   :346
@@ -551,24 +498,19 @@ class GaussianProcess(Estimator):
 			X[:, n0:].zero_()
 		if mp > m:
 			X[m:, :].zero_()
-		tw = torch.empty((int(lib.stpy_trsm_workspace_bytes(dt, mp, n, self.nb)),), dtype=torch.uint8, device=X.device)
-		_lib.check(lib.stpy_trsm_right_lt(dt, mp, n, _lib.ptr(self._L), _lib.ld(self._L), _lib.ptr(self._winv), self._winv.numel(),
-										  _lib.ptr(X), _lib.ld(X), self.nb, 0, _lib.ptr(tw), tw.numel() * tw.element_size(), _lib.stream_ptr()), "stpy_trsm_right_lt")   # X = K* L^-T
+		_lib.trsm_right_lt(X, self._L, self._winv, self.nb, workspace=True)                 # X = K* L^-T
 		return X
 
 	def _predict(self, xt):
 		"""mu, sigma (M,) and X = K* L^-T for device test points against the resident factor (gauss_procc.py:336-401, squared loss)."""
-		lib = _lib.load()
 		xd = self._xd
-		m, n = xt.shape[0], self._L.shape[0]
-		dt = _lib.dtype_code(xd.dtype)
+		m = xt.shape[0]
 		X = self._solve_kstar(xt)
 		mu = torch.empty((m,), dtype=xd.dtype, device=xd.device)
 		kd = torch.empty((m,), dtype=xd.dtype, device=xd.device)
 		self.kernel_object._diag_into(xt, kd)                           # diag k(x*, x*)           :347
 		sigma = torch.empty((m,), dtype=xd.dtype, device=xd.device)
-		_lib.check(lib.stpy_predict(dt, m, n, _lib.ptr(X), _lib.ld(X), _lib.ptr(self._z), _lib.ptr(kd), _lib.ptr(mu),
-									_lib.ptr(sigma), 1 if self.clamp_variance else 0, _lib.stream_ptr()), "stpy_predict")
+		_lib.predict(X[:m], self._z, mu, sigma, kd, 1 if self.clamp_variance else 0)
 		return mu, sigma, X
 
 	# ------------------------------------------------------------------ input gradients (gauss_procc.py:420-459, :918-963)
@@ -586,25 +528,14 @@ class GaussianProcess(Estimator):
 	def _reversed_factor(self):
 		"""J L^T J and its inverse diagonal blocks for B L^-1 (stpy_trsm_ln_factor): another N x N matrix, built once per fit."""
 		if getattr(self, "_Lr", None) is None:
-			lib = _lib.load()
-			L = self._L
-			Lr = torch.empty_like(L)
-			winvr = torch.empty_like(self._winv)
-			_lib.check(lib.stpy_trsm_ln_factor(_lib.dtype_code(L.dtype), L.shape[0], _lib.ptr(L), _lib.ld(L), _lib.ptr(self._winv), self._winv.numel(),
-											   _lib.ptr(Lr), _lib.ld(Lr), _lib.ptr(winvr), _lib.stream_ptr()), "stpy_trsm_ln_factor")
-			self._Lr, self._winvr = Lr, winvr
+			self._Lr, self._winvr = _lib.trsm_ln_factor(self._L, self._winv)
 		return self._Lr, self._winvr
 
 	def _weights_t(self, X):
 		"""W^T = K* K^-1 = X L^-1 (in place over a copy of X): the variance gradient's coefficients, (mp, npad)."""
-		lib = _lib.load()
 		Lr, winvr = self._reversed_factor()
 		W = X.clone()
-		mp, n = W.shape
-		dt = _lib.dtype_code(W.dtype)
-		tw = torch.empty((int(lib.stpy_trsm_workspace_bytes(dt, mp, n, self.nb)),), dtype=torch.uint8, device=W.device)
-		_lib.check(lib.stpy_trsm_right_ln(dt, mp, n, _lib.ptr(Lr), _lib.ld(Lr), _lib.ptr(winvr), winvr.numel(), _lib.ptr(W), _lib.ld(W),
-										  self.nb, 0, _lib.ptr(tw), tw.numel() * tw.element_size(), _lib.stream_ptr()), "stpy_trsm_right_ln")
+		_lib.trsm_right_ln(W, Lr, winvr, self.nb, workspace=True)
 		return W
 
 	def _posterior_grad(self, state, gmu, gstd):
@@ -714,15 +645,13 @@ class GaussianProcess(Estimator):
 		return self._mean_value(xtest)
 
 	def _mean_value(self, xtest):
-		lib = _lib.load()
 		xd = self._xd
 		xt = _lib.to_device(xtest, xd.dtype)
 		m, n = xt.shape[0], self.n
 		Ks = torch.empty((m, n), dtype=xd.dtype, device=xd.device)
 		self.kernel_object._kernel_into(xd, xt, Ks)
 		mu = torch.empty((m,), dtype=xd.dtype, device=xd.device)
-		_lib.check(lib.stpy_predict(_lib.dtype_code(xd.dtype), m, n, _lib.ptr(Ks), _lib.ld(Ks), _lib.ptr(self._alpha), None,
-									_lib.ptr(mu), None, 0, _lib.stream_ptr()), "stpy_predict")
+		_lib.predict(Ks, self._alpha, mu)
 		return _lib.like_input(mu.reshape(-1, 1), xtest)
 
 	# ------------------------------------------------------------------ sampling
@@ -734,7 +663,6 @@ class GaussianProcess(Estimator):
 		and a seeded run here see the same random_vector; the M x M Cholesky and the product run in
 		stpy_potrf / stpy_gemm_nt.
 		"""
-		lib = _lib.load()
 		nn = list(xtest.size())[0]
 		if self.fitted == True:
 			(ymean, cov) = self.mean_std(xtest, full=True)
@@ -745,16 +673,10 @@ class GaussianProcess(Estimator):
 			eps = jitter
 		cov = _lib.to_device(cov)
 		C = torch.empty_like(cov)
-		dt = _lib.dtype_code(C.dtype)
-		_lib.check(lib.stpy_combine(dt, nn, nn, _lib.ptr(C), _lib.ld(C), _lib.ptr(cov), _lib.ld(cov), _lib.OUT_SET, eps, _lib.stream_ptr()), "stpy_combine")      # C = cov + eps I
-		winv = torch.empty((int(lib.stpy_potrf_winv_elems(nn)),), dtype=C.dtype, device=C.device)
-		work = torch.empty((int(lib.stpy_potrf_workspace_bytes(dt, nn, self.nb)),), dtype=torch.uint8, device=C.device)
-		info = torch.zeros((1,), dtype=torch.int32, device=C.device)
-		_lib.check(lib.stpy_potrf(dt, nn, _lib.ptr(C), _lib.ld(C), _lib.ptr(winv), winv.numel(), _lib.ptr(work), work.numel() * work.element_size(), self.nb, 0, _lib.ptr(info), _lib.stream_ptr()), "stpy_potrf")
-		bad = int(info.item())
-		if bad != 0:
-			raise torch.linalg.LinAlgError("sample: posterior covariance + jitter is not positive definite (leading minor %d)" % bad)
-		_lib.check(lib.stpy_tril(dt, nn, _lib.ptr(C), _lib.ld(C), _lib.stream_ptr()), "stpy_tril")      # the strict upper triangle of an in-place factor is scratch
+		_lib.combine(C, cov, _lib.OUT_SET, eps)                                        # C = cov + eps I
+		_, info = _lib.potrf(C, self.nb)
+		self._check_info(info, "sample: posterior covariance + jitter is not positive definite (leading minor %d)")
+		_lib.tril(C)                        # the strict upper triangle of an in-place factor is scratch
 		random_vector = torch.normal(mean=torch.zeros(nn, size, dtype=torch.float64), std=1.)
 		rt = random_vector.T.contiguous().to(device=C.device, dtype=C.dtype)          # (size, nn): the NT operand
 		# f = ymean + L r: the accumulating product on a result that starts as the mean in every column
@@ -763,8 +685,7 @@ class GaussianProcess(Estimator):
 			f.copy_(_lib.to_device(ymean, C.dtype).reshape(nn, 1).expand(nn, size))
 		else:
 			f.fill_(float(ymean))
-		_lib.check(lib.stpy_gemm_nt(dt, nn, size, nn, _lib.ptr(C), _lib.ld(C), _lib.ptr(rt), _lib.ld(rt), _lib.ptr(f), _lib.ld(f), 2, 0,
-									_lib.stream_ptr()), "stpy_gemm_nt")
+		_lib.gemm_nt(C, rt, f, 2)
 		return _lib.like_input(f, xtest)
 
 	def sample_and_max(self, xtest, size=1):
@@ -807,7 +728,6 @@ class GaussianProcess(Estimator):
 		return out
 
 	def _log_marginal_value(self, kernel, X, weight):
-		lib = _lib.load()
 		if self._xd is None:
 			if self.x is None:
 				raise AttributeError("log_marginal needs data: call fit_gp or load_data first")
@@ -825,10 +745,8 @@ class GaussianProcess(Estimator):
 				L, winv = self._factor(self._xd, X, None)
 			finally:
 				self.kernel_object = saved
-			z = self._forward_y(L, winv, self._yd)
-		out2 = torch.empty((2,), dtype=L.dtype, device=L.device)
-		_lib.check(lib.stpy_logdet_quad(_lib.dtype_code(L.dtype), L.shape[0], _lib.ptr(L), _lib.ld(L), _lib.ptr(z), _lib.ptr(out2),
-										_lib.stream_ptr()), "stpy_logdet_quad")
+			z = _lib.trsv(L, winv, self._yd)
+		out2 = _lib.logdet_quad(L, z)
 		w = float(weight) if not torch.is_tensor(weight) else float(weight.item())
 		logdiag, quad = out2.tolist()                                                   # sum log L_ii, z^T z: host scalars
 		val = torch.full((1, 1), 0.5 * quad + 0.5 * w * 2.0 * logdiag, dtype=L.dtype, device=L.device)
@@ -847,25 +765,20 @@ class GaussianProcess(Estimator):
 		sum_ij H_ij u_m^2 = 2 [ sum_i xs_im^2 h_i - xs_m^T H xs_m ] with h = H 1 -- one stpy_gemm_nt of H
 		against [Xs | 1].
 		"""
-		lib = _lib.load()
 		from ..kernels import _dev_const
 		L, winv, z = state
 		npad = L.shape[0]                               # tile-padded order of the factor (see _factor)
-		dt = _lib.dtype_code(L.dtype)
 		items = kernel._resolve(dict(X) if X else {})
 		w = float(weight) if not torch.is_tensor(weight) else float(weight.item())
-		st = _lib.stream_ptr
 		xd = self._xd
 		n = xd.shape[0]
-		alpha = self._backward_z(L, winv, z)[:n]
-		Kinv_p = torch.empty((npad, npad), dtype=L.dtype, device=L.device)
+		alpha = _lib.trsv(L, winv, z, trans=1)[:n]
+		# inverse of the bordered matrix = [[K^-1, 0], [0, I]]: everything below works on the leading n x n views (the potri
+		# workspace is kept as the scratch H of several kernel terms)
 		work_p = torch.empty((npad, npad), dtype=L.dtype, device=L.device)
-		_lib.check(lib.stpy_potri(dt, npad, _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(Kinv_p), _lib.ld(Kinv_p), _lib.ptr(work_p), work_p.numel() * work_p.element_size(), st()), "stpy_potri")
-		# inverse of the bordered matrix = [[K^-1, 0], [0, I]]: everything below works on the leading n x n views
-		Kinv, work = Kinv_p[:n, :n], work_p[:n, :n]
-		_lib.check(lib.stpy_symmetrize_lower(dt, n, _lib.ptr(Kinv), _lib.ld(Kinv), st()), "stpy_symmetrize_lower")
-		td = torch.empty((2,), dtype=L.dtype, device=L.device)                           # tr(K^-1), alpha^T alpha: fixed-order reduction
-		_lib.check(lib.stpy_trace_dot(dt, n, _lib.ptr(Kinv), _lib.ld(Kinv), _lib.ptr(alpha), _lib.ptr(alpha), _lib.ptr(td), st()), "stpy_trace_dot")
+		Kinv = _lib.potri(L, winv, n, work=work_p)
+		work = work_p[:n, :n]
+		td = _lib.trace_dot(Kinv, alpha, alpha)                                          # tr(K^-1), alpha^T alpha: fixed-order reduction
 
 		wanted = [(key, name, t) for (key, name, t) in params if key != "likelihood"]
 		single = len(items) == 1 and len(items[0]['terms']) == 1
@@ -893,10 +806,7 @@ class GaussianProcess(Estimator):
 				# H <- (w K^-1 - alpha alpha^T) o kappa F_t: in place over K^-1 when this is the only term, otherwise written
 				# to `work` with K^-1 only read (no N x N copy)
 				H = Kinv if single else work
-				ws = torch.empty((int(lib.stpy_gram_workspace_bytes(dt, n, n, kd)),), dtype=torch.uint8, device=xd.device)
-				_lib.check(lib.stpy_lml_weight(term['kind'], dt, _lib.ptr(kx), n, _lib.ld(kx), kd, _lib.ptr(kcols), _lib.ptr(inv_ls),
-											   term['kappa'], w, _lib.ptr(alpha), _lib.ptr(Kinv), _lib.ld(Kinv), _lib.ptr(H), _lib.ld(H),
-											   _lib.ptr(ws), ws.numel() * ws.element_size(), st()), "stpy_lml_weight")
+				_lib.lml_weight(term['kind'], kx, inv_ls, term['kappa'], w, alpha, Kinv, H, cols=kcols)
 				# ... o M_i
 				factors = []
 				if it['op'] == "*" and i > 0:
@@ -912,23 +822,20 @@ class GaussianProcess(Estimator):
 					if tmp is None:
 						tmp = torch.empty((n, n), dtype=L.dtype, device=L.device)
 					kernel._run_items(fac, xd, xd, tmp)
-					_lib.check(lib.stpy_combine(dt, n, n, _lib.ptr(H), _lib.ld(H), _lib.ptr(tmp), _lib.ld(tmp), _lib.OUT_MUL, 0.0, st()), "stpy_combine")
+					_lib.combine(H, tmp, _lib.OUT_MUL)
 				# [Xs | 1]^T (dg + 1, n): scaled coordinates as the NT operand, then P = H [Xs | 1] and the per-coordinate sums
 				dg = kd
-				XT = torch.empty((dg + 1, n), dtype=xd.dtype, device=xd.device)
-				_lib.check(lib.stpy_scaled_points_t(dt, _lib.ptr(kx), n, _lib.ld(kx), dg, _lib.ptr(kcols), _lib.ptr(inv_ls), _lib.ptr(XT), _lib.ld(XT), 1, st()), "stpy_scaled_points_t")
+				XT = _lib.scaled_points_t(kx, inv_ls, kcols)
 				P = torch.empty((n, dg + 1), dtype=xd.dtype, device=xd.device)
-				_lib.check(lib.stpy_gemm_nt(dt, n, dg + 1, n, _lib.ptr(H), _lib.ld(H), _lib.ptr(XT), _lib.ld(XT), _lib.ptr(P), _lib.ld(P), 0, 0, st()), "stpy_gemm_nt")
+				_lib.gemm_nt(H, XT, P)
 				a_ = acc[(str(i), term['pname'])]
 				if premap is not None:
 					if a_.numel() != len(group) * dg:
 						raise ValueError("evidence gradient: 'cov' has %d entries, the item maps %d columns to %d" % (a_.numel(), len(group), dg))
-					_lib.check(lib.stpy_lml_grad_cov_reduce(dt, _lib.ptr(xd), n, _lib.ld(xd), len(group), _lib.ptr(cols), _lib.ptr(kx), _lib.ld(kx), dg,
-															_lib.ptr(P), _lib.ld(P), _lib.ptr(a_), st()), "stpy_lml_grad_cov_reduce")
+					_lib.lml_grad_cov_reduce(xd, kx, P, a_, cols)
 					continue
 				pidx = _dev_const([int(v) for v in term['pidx']], None, xd.device, int32=True)
-				_lib.check(lib.stpy_lml_grad_reduce(dt, _lib.ptr(xd), n, _lib.ld(xd), dg, _lib.ptr(cols), _lib.ptr(inv_ls), _lib.ptr(P), _lib.ld(P),
-													_lib.ptr(pidx), _lib.ptr(a_), st()), "stpy_lml_grad_reduce")
+				_lib.lml_grad_reduce(xd, inv_ls, P, pidx, a_, cols)
 		del work, work_p
 		for key, name, t in wanted:
 			if (key, name) not in acc or int(key) >= len(items) or not any(tm['pname'] == name for tm in items[int(key)]['terms']):

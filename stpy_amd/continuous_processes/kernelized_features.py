@@ -126,16 +126,12 @@ class KernelizedFeatures(GaussianProcess):
 
 	def _first_feature_kernel(self, x, y, diag_add=0.0):
 		"""(|y|, |x|) linear kernel of the FIRST feature only (see the module header), + diag_add on the diagonal; device tensor."""
-		lib = _lib.load()
 		ex = _lib.to_device(self.embed(_lib.to_device(x)))[:, :1].contiguous()
 		ey = _lib.to_device(self.embed(_lib.to_device(y)), ex.dtype)[:, :1].contiguous()
 		out = torch.empty((ey.shape[0], ex.shape[0]), dtype=ex.dtype, device=ex.device)
-		dt = _lib.dtype_code(ex.dtype)
-		_lib.check(lib.stpy_gemm_nt(dt, ey.shape[0], ex.shape[0], ex.shape[1], _lib.ptr(ey), _lib.ld(ey), _lib.ptr(ex), _lib.ld(ex),
-									_lib.ptr(out), _lib.ld(out), 0, 0, _lib.stream_ptr()), "stpy_gemm_nt")
+		_lib.gemm_nt(ey, ex, out)
 		if diag_add != 0.0:
-			_lib.check(lib.stpy_combine(dt, out.shape[0], out.shape[1], _lib.ptr(out), _lib.ld(out), _lib.ptr(out), _lib.ld(out), _lib.OUT_SET, diag_add,
-										_lib.stream_ptr()), "stpy_combine")
+			_lib.combine(out, out, _lib.OUT_SET, diag_add)
 		return out
 
 	def kernel(self, x, y):
@@ -146,40 +142,27 @@ class KernelizedFeatures(GaussianProcess):
 		"""kernelized_features.py:553-557."""
 		return _lib.like_input(self._first_feature_kernel(self.x, self.x, float(self.s) ** 2 * float(self.lam)), self.x)
 
-	def _logdet_factor(self):
-		"""2 sum log L_ii of the resident factor, host scalar."""
-		lib = _lib.load()
-		L = self._Lf
-		out2 = torch.empty((2,), dtype=L.dtype, device=L.device)
-		_lib.check(lib.stpy_logdet_quad(_lib.dtype_code(L.dtype), L.shape[0], _lib.ptr(L), _lib.ld(L), None, _lib.ptr(out2), _lib.stream_ptr()), "stpy_logdet_quad")
-		return 2.0 * float(out2[0].item())
-
 	def logdet_ratio(self):
 		"""kernelized_features.py:99-101: logdet(self.K) - logdet(s^2 lam I_m)."""
 		self.precompute()
 		m = self.get_basis_size()
-		ld = self._logdet_factor() if (self.dual and self.fitted) else 0.0        # primal: K is the ones(1, 1) placeholder
+		ld = 2.0 * float(_lib.logdet_quad(self._Lf)[0].item()) if (self.dual and self.fitted) else 0.0        # primal: K is the ones(1, 1) placeholder
 		return torch.tensor(ld - m * math.log(float(self.s) ** 2 * float(self.lam)), dtype=torch.float64)
 
 	def effective_dim(self, xtest):
 		"""kernelized_features.py:103-106: tr((Phi^T Phi + lam I)^-1 Phi^T Phi) = m - lam tr((Phi^T Phi + lam I)^-1)
 		(the reference line calls torch.solve, which current torch no longer has; this is what it computes)."""
-		lib = _lib.load()
 		xt = _lib.to_device(xtest)
 		PhiT = _lib.to_device(self._embed_t(xt), xt.dtype)
 		if PhiT.stride(1) != 1:
 			PhiT = PhiT.contiguous()
-		m, k = PhiT.shape
-		dt = _lib.dtype_code(PhiT.dtype)
-		st = _lib.stream_ptr
+		m = PhiT.shape[0]
 		A = torch.empty((m, m), dtype=PhiT.dtype, device=PhiT.device)
-		_lib.check(lib.stpy_gemm_nt(dt, m, m, k, _lib.ptr(PhiT), _lib.ld(PhiT), _lib.ptr(PhiT), _lib.ld(PhiT), _lib.ptr(A), _lib.ld(A), 0, 1, st()), "stpy_gemm_nt")
-		_lib.check(lib.stpy_combine(dt, m, m, _lib.ptr(A), _lib.ld(A), _lib.ptr(A), _lib.ld(A), _lib.OUT_SET, float(self.lam), st()), "stpy_combine")
+		_lib.gemm_nt(PhiT, PhiT, A, lower_only=True)
+		_lib.combine(A, A, _lib.OUT_SET, float(self.lam))
 		L, winv = self._chol(A, "effective_dim: Phi^T Phi + lam I")
-		inv = self._inverse_from_factor(L, winv)
-		td = torch.empty((2,), dtype=inv.dtype, device=inv.device)
-		_lib.check(lib.stpy_trace_dot(dt, m, _lib.ptr(inv), _lib.ld(inv), None, None, _lib.ptr(td), st()), "stpy_trace_dot")
-		return torch.tensor(m - float(self.lam) * float(td[0].item()), dtype=torch.float64)
+		inv = _lib.potri(L, winv)
+		return torch.tensor(m - float(self.lam) * float(_lib.trace_dot(inv)[0].item()), dtype=torch.float64)
 
 	def beta(self, delta=0.1, norm=None):
 		"""kernelized_features.py:56-76."""
@@ -193,7 +176,7 @@ class KernelizedFeatures(GaussianProcess):
 			self.precompute()
 			m = self.get_basis_size()
 			c = float(self.s) ** 2 * float(self.lam)
-			ldV = self._logdet_factor() + ((m - self.n) * math.log(c) if self.dual else 0.0)
+			ldV = 2.0 * float(_lib.logdet_quad(self._Lf)[0].item()) + ((m - self.n) * math.log(c) if self.dual else 0.0)
 			val = float(self.bound) * float(self.lam) + ldV - m * math.log(float(self.s) ** 2) - m * math.log(float(self.lam)) + 2 * np.log(1 / delta)
 			return torch.tensor(val, dtype=torch.float64)
 		return self.beta_fun(self.K, delta=delta, norm=norm)
@@ -270,11 +253,8 @@ class KernelizedFeatures(GaussianProcess):
 
 	def _accumulate(self, xd, yd, first):
 		"""V_acc (+)= Phi^T Phi (lower tiles) and rhs (+)= Phi^T y over row slabs of xd; ``first``: the buffers are (re)created."""
-		lib = _lib.load()
 		n = xd.shape[0]
 		esz = xd.element_size()
-		st = _lib.stream_ptr
-		dt = _lib.dtype_code(xd.dtype)
 		m = None if first else self._Vacc.shape[0]
 		rows = n if first else max(128, (int(self.slab_bytes) // (m * esz)) // 128 * 128)
 		r0 = 0
@@ -299,125 +279,75 @@ class KernelizedFeatures(GaussianProcess):
 			V = self._Vacc
 			# V (+)= Phi_slab^T Phi_slab, lower tiles only: mode 0 for the first slab of a fit, 2 (accumulate) afterwards
 			# (fp32 slabs of 2048 features and more: the slab is split once into bf16 planes in a workspace and every output tile reads those)
-			wb = int(lib.stpy_syrk_workspace_bytes(dt, m, take))
-			work = torch.empty((wb,), dtype=torch.uint8, device=PhiT.device) if wb > 0 else None
-			_lib.check(lib.stpy_syrk(dt, m, take, _lib.ptr(PhiT), _lib.ld(PhiT), _lib.ptr(V), _lib.ld(V), 0 if first else 2,
-									 _lib.ptr(work) if work is not None else None, wb, st()), "stpy_syrk")
-			del work
+			_lib.syrk(PhiT, V, 0 if first else 2)
 			# Phi_slab^T y_slab: row sums of Phi^T against y
 			ys = yd[r0:r0 + take]
 			tgt = self._rhs if first else self._part
-			_lib.check(lib.stpy_predict(dt, m, take, _lib.ptr(PhiT), _lib.ld(PhiT), _lib.ptr(ys), None, _lib.ptr(tgt), None, 0, st()), "stpy_predict")
+			_lib.predict(PhiT, ys, tgt)
 			if not first:
-				_lib.check(lib.stpy_combine(dt, 1, m, _lib.ptr(self._rhs), m, _lib.ptr(self._part), m, _lib.OUT_ADD, 0.0, st()), "stpy_combine")
+				_lib.combine(self._rhs, self._part, _lib.OUT_ADD)
 			first = False
 			r0 += take
 			del PhiT
 
 	def _chol(self, A, what, keep=None):
 		"""In-place stpy_potrf of A; returns (A, winv).  Raises LinAlgError (and leaves the object unfitted) on a failing pivot."""
-		lib = _lib.load()
-		n = A.shape[0]
-		dt = _lib.dtype_code(A.dtype)
-		winv = torch.empty((int(lib.stpy_potrf_winv_elems(n)),), dtype=A.dtype, device=A.device)
-		work = torch.empty((int(lib.stpy_potrf_workspace_bytes(dt, n, self.nb)),), dtype=torch.uint8, device=A.device)
-		info = torch.zeros((1,), dtype=torch.int32, device=A.device)
-		_lib.check(lib.stpy_potrf(dt, n, _lib.ptr(A), _lib.ld(A), _lib.ptr(winv), winv.numel(), _lib.ptr(work), work.numel() * work.element_size(), self.nb, 0, _lib.ptr(info),
-								  _lib.stream_ptr()), "stpy_potrf")
-		bad = int(info.item())
-		if bad != 0:
-			raise torch.linalg.LinAlgError("KernelizedFeatures: %s is not positive definite (leading minor %d)" % (what, bad))
+		winv, info = _lib.potrf(A, self.nb)
+		self._check_info(info, "KernelizedFeatures: " + what + " is not positive definite (leading minor %d)")
 		return A, winv
-
-	def _solve_pair(self, L, winv, rhs):
-		"""u = L^-1 rhs, v = L^-T u (rhs is copied: stpy_trsv uses its right-hand side as scratch)."""
-		lib = _lib.load()
-		n = L.shape[0]
-		dt = _lib.dtype_code(L.dtype)
-		st = _lib.stream_ptr
-		r = rhs.reshape(-1).clone()
-		u = torch.empty_like(r)
-		_lib.check(lib.stpy_trsv(dt, n, _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(r), _lib.ptr(u), 0, st()), "stpy_trsv")
-		scratch = u.clone()
-		v = torch.empty_like(u)
-		_lib.check(lib.stpy_trsv(dt, n, _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(scratch), _lib.ptr(v), 1, st()), "stpy_trsv")
-		_lib.check_async("KernelizedFeatures: stpy_trsv")           # a hand-off wait that gave up has poisoned u / v with NaN
-		return u, v
 
 	def _solve_normal_equations(self):
 		"""V = V_acc + s^2 lam I -> Cholesky, u = L^-1 (Phi^T y), theta = L^-T u."""
-		lib = _lib.load()
-		Vacc = self._Vacc
-		m = Vacc.shape[0]
-		dt = _lib.dtype_code(Vacc.dtype)
-		V = torch.empty_like(Vacc)
+		V = torch.empty_like(self._Vacc)
 		# V = V_acc, then + s^2 lam on the diagonal (one pass of the elementwise kernel)
-		_lib.check(lib.stpy_combine(dt, m, m, _lib.ptr(V), _lib.ld(V), _lib.ptr(Vacc), _lib.ld(Vacc), _lib.OUT_SET, float(self.s) ** 2 * float(self.lam), _lib.stream_ptr()), "stpy_combine")
+		_lib.combine(V, self._Vacc, _lib.OUT_SET, float(self.s) ** 2 * float(self.lam))
 		self.fitted = False
 		L, winv = self._chol(V, "Phi^T Phi + s^2 lam I")
-		u, theta = self._solve_pair(L, winv, self._rhs)
+		u = _lib.trsv(L, winv, self._rhs)
+		theta = _lib.trsv(L, winv, u, trans=1)
+		_lib.check_async("KernelizedFeatures: stpy_trsv")           # a hand-off wait that gave up has poisoned u / theta with NaN
 		self._Lf, self._winvf, self._u, self._theta = L, winv, u, theta
 		self.fitted = True
 
 	def _dual_K(self):
 		"""Phi Phi^T + s^2 lam I (n x n, full) from the kept Phi^T."""
-		lib = _lib.load()
 		Phi = self._PhiT.t().contiguous()                                 # (n, m); n < m
-		n, m = Phi.shape
-		dt = _lib.dtype_code(Phi.dtype)
+		n = Phi.shape[0]
 		K = torch.empty((n, n), dtype=Phi.dtype, device=Phi.device)
-		_lib.check(lib.stpy_gemm_nt(dt, n, n, m, _lib.ptr(Phi), _lib.ld(Phi), _lib.ptr(Phi), _lib.ld(Phi), _lib.ptr(K), _lib.ld(K), 0, 0, _lib.stream_ptr()), "stpy_gemm_nt")
-		_lib.check(lib.stpy_combine(dt, n, n, _lib.ptr(K), _lib.ld(K), _lib.ptr(K), _lib.ld(K), _lib.OUT_SET, float(self.s) ** 2 * float(self.lam), _lib.stream_ptr()), "stpy_combine")
+		_lib.gemm_nt(Phi, Phi, K)
+		_lib.combine(K, K, _lib.OUT_SET, float(self.s) ** 2 * float(self.lam))
 		return K
 
 	def _fit_dual(self, xd, yd):
 		"""kernelized_features.py:229-235, :252-254: K = Q Q^T + s^2 lam I -> Cholesky, z = L^-1 y, theta = Q^T K^-1 y."""
-		lib = _lib.load()
 		PhiT = _lib.to_device(self._embed_t(xd), xd.dtype)                # (m, n)
 		if PhiT.stride(1) != 1:
 			PhiT = PhiT.contiguous()
 		self._PhiT = PhiT
 		self.fitted = False
 		L, winv = self._chol(self._dual_K(), "Phi Phi^T + s^2 lam I")
-		z, alpha = self._solve_pair(L, winv, yd)
-		m, n = PhiT.shape
-		theta = torch.empty((m,), dtype=PhiT.dtype, device=PhiT.device)
-		_lib.check(lib.stpy_predict(_lib.dtype_code(PhiT.dtype), m, n, _lib.ptr(PhiT), _lib.ld(PhiT), _lib.ptr(alpha), None, _lib.ptr(theta), None, 0,
-									_lib.stream_ptr()), "stpy_predict")                             # theta = Phi^T alpha
+		z = _lib.trsv(L, winv, yd)
+		alpha = _lib.trsv(L, winv, z, trans=1)
+		_lib.check_async("KernelizedFeatures: stpy_trsv")           # a hand-off wait that gave up has poisoned z / alpha with NaN
+		theta = torch.empty((PhiT.shape[0],), dtype=PhiT.dtype, device=PhiT.device)
+		_lib.predict(PhiT, alpha, theta)                                  # theta = Phi^T alpha
 		self._Lf, self._winvf, self._u, self._theta = L, winv, z, theta
 		self.fitted = True
 
 	# ------------------------------------------------------------------ V, V^-1
-	def _inverse_from_factor(self, L, winv):
-		"""(L L^T)^-1, full symmetric, device."""
-		lib = _lib.load()
-		m = L.shape[0]
-		dt = _lib.dtype_code(L.dtype)
-		out = torch.empty((m, m), dtype=L.dtype, device=L.device)
-		work = torch.empty((m, m), dtype=L.dtype, device=L.device)
-		_lib.check(lib.stpy_potri(dt, m, _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(out), _lib.ld(out), _lib.ptr(work), work.numel() * work.element_size(),
-								  _lib.stream_ptr()), "stpy_potri")
-		_lib.check(lib.stpy_symmetrize_lower(dt, m, _lib.ptr(out), _lib.ld(out), _lib.stream_ptr()), "stpy_symmetrize_lower")
-		return out
-
 	def _V_device(self):
 		"""The matrix ``self.V`` of the reference: primal Phi^T Phi + s^2 lam I (:239); dual the first-column form of get_invV (:167-170)."""
-		lib = _lib.load()
 		c = float(self.s) ** 2 * float(self.lam)
 		if self.dual:
 			q0 = self._PhiT[:, :1].contiguous()                          # Q^T[:, group = [0]]: the features of the first data point
 			m = q0.shape[0]
-			dt = _lib.dtype_code(q0.dtype)
 			V = torch.empty((m, m), dtype=q0.dtype, device=q0.device)
-			_lib.check(lib.stpy_gemm_nt(dt, m, m, 1, _lib.ptr(q0), 1, _lib.ptr(q0), 1, _lib.ptr(V), _lib.ld(V), 0, 0, _lib.stream_ptr()), "stpy_gemm_nt")
-			_lib.check(lib.stpy_combine(dt, m, m, _lib.ptr(V), _lib.ld(V), _lib.ptr(V), _lib.ld(V), _lib.OUT_SET, c, _lib.stream_ptr()), "stpy_combine")
+			_lib.gemm_nt(q0, q0, V)
+			_lib.combine(V, V, _lib.OUT_SET, c)
 			return V
-		Vacc = self._Vacc
-		m = Vacc.shape[0]
-		dt = _lib.dtype_code(Vacc.dtype)
-		V = torch.empty_like(Vacc)
-		_lib.check(lib.stpy_combine(dt, m, m, _lib.ptr(V), _lib.ld(V), _lib.ptr(Vacc), _lib.ld(Vacc), _lib.OUT_SET, c, _lib.stream_ptr()), "stpy_combine")
-		_lib.check(lib.stpy_symmetrize_lower(dt, m, _lib.ptr(V), _lib.ld(V), _lib.stream_ptr()), "stpy_symmetrize_lower")
+		V = torch.empty_like(self._Vacc)
+		_lib.combine(V, self._Vacc, _lib.OUT_SET, c)
+		_lib.symmetrize_lower(V)
 		return V
 
 	@property
@@ -430,8 +360,8 @@ class KernelizedFeatures(GaussianProcess):
 		if self.dual:
 			V = self._V_device()
 			L, winv = self._chol(V, "V (dual get_invV)")
-			return self._inverse_from_factor(L, winv)
-		return self._inverse_from_factor(self._Lf, self._winvf)
+			return _lib.potri(L, winv)
+		return _lib.potri(self._Lf, self._winvf)
 
 	@property
 	def invV(self):
@@ -445,7 +375,6 @@ class KernelizedFeatures(GaussianProcess):
 
 	def theta_mean(self, var=False, prior=False):
 		"""kernelized_features.py:248-264."""
-		lib = _lib.load()
 		self.precompute()
 		if self.fitted and not prior:
 			theta = _lib.like_input(self._theta.reshape(-1, 1), self.x)
@@ -460,16 +389,14 @@ class KernelizedFeatures(GaussianProcess):
 			return (theta, Z)
 		# dual: Z = invK_V = (I - Q^T K^-1 Q) / lam = (I - W W^T) / lam with W = Q^T L^-T  (m x n)
 		L = self._Lf
-		m, n = self._PhiT.shape
-		dt = _lib.dtype_code(L.dtype)
-		st = _lib.stream_ptr
+		m = self._PhiT.shape[0]
 		W = self._PhiT.clone()
-		_lib.check(lib.stpy_trsm_right_lt(dt, m, n, _lib.ptr(L), _lib.ld(L), _lib.ptr(self._winvf), self._winvf.numel(), _lib.ptr(W), _lib.ld(W), self.nb, 0, None, 0, st()), "stpy_trsm_right_lt")
+		_lib.trsm_right_lt(W, L, self._winvf, self.nb)
 		Z = torch.eye(m, dtype=L.dtype, device=L.device)
-		_lib.check(lib.stpy_gemm_nt(dt, m, m, n, _lib.ptr(W), _lib.ld(W), _lib.ptr(W), _lib.ld(W), _lib.ptr(Z), _lib.ld(Z), 1, 0, st()), "stpy_gemm_nt")
+		_lib.gemm_nt(W, W, Z, 1)
 		if float(self.lam) != 1.0:
 			inv_lam = torch.full((m, m), 1.0 / float(self.lam), dtype=L.dtype, device=L.device)
-			_lib.check(lib.stpy_combine(dt, m, m, _lib.ptr(Z), _lib.ld(Z), _lib.ptr(inv_lam), _lib.ld(inv_lam), _lib.OUT_MUL, 0.0, st()), "stpy_combine")
+			_lib.combine(Z, inv_lam, _lib.OUT_MUL)
 		return (theta, _lib.like_input(Z, self.x))
 
 	# ------------------------------------------------------------------ predict
@@ -478,37 +405,34 @@ class KernelizedFeatures(GaussianProcess):
 
 	def mean_std(self, xtest):
 		"""kernelized_features.py:269-288."""
-		lib = _lib.load()
 		self.precompute()
 		L = self._Lf
 		xt = _lib.to_device(xtest, L.dtype)
 		Phi = _lib.to_device(self.embedding.embed(xt), L.dtype)          # (M, m): rows = right-hand sides
 		if Phi.stride(1) != 1:
 			Phi = Phi.contiguous()
-		M, m = Phi.shape
-		dt = _lib.dtype_code(L.dtype)
-		st = _lib.stream_ptr
+		M = Phi.shape[0]
 		mu, ss = torch.empty((M,), dtype=L.dtype, device=L.device), torch.empty((M,), dtype=L.dtype, device=L.device)
 		std = torch.empty_like(ss)
 		if not self.dual:
 			X = Phi.clone()
-			_lib.check(lib.stpy_trsm_right_lt(dt, M, m, _lib.ptr(L), _lib.ld(L), _lib.ptr(self._winvf), self._winvf.numel(), _lib.ptr(X), _lib.ld(X), self.nb, 0, None, 0, st()), "stpy_trsm_right_lt")
-			_lib.check(lib.stpy_predict(dt, M, m, _lib.ptr(X), _lib.ld(X), _lib.ptr(self._u), None, _lib.ptr(mu), _lib.ptr(ss), 2, st()), "stpy_predict")
+			_lib.trsm_right_lt(X, L, self._winvf, self.nb)
+			_lib.predict(X, self._u, mu, ss, clamp=2)
 			# std = s sqrt(ss) = sqrt(0 - (-s^2) ss): the prediction epilogue with a zero prior term (no torch arithmetic on the vectors)
-			_lib.check(lib.stpy_predict_finish(dt, M, None, _lib.ptr(ss), _lib.ptr(torch.zeros_like(ss)), -float(self.s) ** 2, _lib.ptr(std), 0, st()), "stpy_predict_finish")
+			_lib.predict_finish(sumsq=ss, kdiag=torch.zeros_like(ss), scale=-float(self.s) ** 2, sigma=std)
 			return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(std.reshape(-1, 1), xtest))
 		# dual: K* = Phi* Phi^T (M x n), X = K* L^-T, mean = X z, var = (|phi*|^2 - rowsum(X o X)) / lam
 		PhiTr = self._PhiT.t().contiguous()                               # (n, m)
 		n = PhiTr.shape[0]
 		X = torch.empty((M, n), dtype=L.dtype, device=L.device)
-		_lib.check(lib.stpy_gemm_nt(dt, M, n, m, _lib.ptr(Phi), _lib.ld(Phi), _lib.ptr(PhiTr), _lib.ld(PhiTr), _lib.ptr(X), _lib.ld(X), 0, 0, st()), "stpy_gemm_nt")
-		_lib.check(lib.stpy_trsm_right_lt(dt, M, n, _lib.ptr(L), _lib.ld(L), _lib.ptr(self._winvf), self._winvf.numel(), _lib.ptr(X), _lib.ld(X), self.nb, 0, None, 0, st()), "stpy_trsm_right_lt")
-		_lib.check(lib.stpy_predict(dt, M, n, _lib.ptr(X), _lib.ld(X), _lib.ptr(self._u), None, _lib.ptr(mu), _lib.ptr(ss), 2, st()), "stpy_predict")
+		_lib.gemm_nt(Phi, PhiTr, X)
+		_lib.trsm_right_lt(X, L, self._winvf, self.nb)
+		_lib.predict(X, self._u, mu, ss, clamp=2)
 		kd = torch.empty_like(ss)                                         # |phi*|^2: the same row-sum kernel on Phi*
-		_lib.check(lib.stpy_predict(dt, M, m, _lib.ptr(Phi), _lib.ld(Phi), _lib.ptr(self._theta), None, None, _lib.ptr(kd), 2, st()), "stpy_predict")
-		_lib.check(lib.stpy_predict_finish(dt, M, None, _lib.ptr(ss), _lib.ptr(kd), 1.0, _lib.ptr(std), 1 if self.clamp_variance else 0, st()), "stpy_predict_finish")
+		_lib.predict(Phi, self._theta, sigma=kd, clamp=2)
+		_lib.predict_finish(sumsq=ss, kdiag=kd, scale=1.0, sigma=std, clamp=1 if self.clamp_variance else 0)
 		if float(self.lam) != 1.0:                                        # ... / sqrt(lam): the epilogue's scale on a vector
-			_lib.check(lib.stpy_predict_finish(dt, M, _lib.ptr(std), None, None, 1.0 / math.sqrt(float(self.lam)), None, 0, st()), "stpy_predict_finish")
+			_lib.predict_finish(mu=std, scale=1.0 / math.sqrt(float(self.lam)))
 		return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(std.reshape(-1, 1), xtest))
 
 	mean_var = mean_std
@@ -531,18 +455,13 @@ class KernelizedFeatures(GaussianProcess):
 
 	def residuals(self):
 		"""kernelized_features.py:559-562: sum (mean(x) - y)^2."""
-		lib = _lib.load()
 		mu, _ = self.mean_std(self.x)
 		r = _lib.to_device(mu).reshape(-1, 1).clone()
 		y = _lib.to_device(self.y, r.dtype).reshape(-1, 1).contiguous()
-		dt = _lib.dtype_code(r.dtype)
 		one = torch.ones((1, 1), dtype=r.dtype, device=r.device)
-		n = r.shape[0]
 		# r -= y 1^T (a K = 1 product in the subtracting mode), then <r, r>
-		_lib.check(lib.stpy_gemm_nt(dt, n, 1, 1, _lib.ptr(y), 1, _lib.ptr(one), 1, _lib.ptr(r), 1, 1, 0, _lib.stream_ptr()), "stpy_gemm_nt")
-		td = torch.empty((2,), dtype=r.dtype, device=r.device)
-		_lib.check(lib.stpy_trace_dot(dt, n, None, 0, _lib.ptr(r), _lib.ptr(r), _lib.ptr(td), _lib.stream_ptr()), "stpy_trace_dot")
-		return _lib.like_input(td[1].reshape(()).clone(), self.x)
+		_lib.gemm_nt(y, one, r, 1)
+		return _lib.like_input(_lib.trace_dot(u=r, v=r)[1].reshape(()).clone(), self.x)
 
 	# ------------------------------------------------------------------ sampling (SURVEY.md section 8f rank 3)
 	def _draw(self, basis, size):
@@ -560,7 +479,6 @@ class KernelizedFeatures(GaussianProcess):
 
 	def _sample_theta_t(self, size=1, prior=False):
 		"""theta^T on the device, (size, basis)."""
-		lib = _lib.load()
 		basis = self.get_basis_size()
 		random_vector = self._draw(basis, size)
 		self.precompute()
@@ -571,14 +489,12 @@ class KernelizedFeatures(GaussianProcess):
 		# L = chol(get_invV()) * s, theta = theta_mean + L r  (:328-330).  theta^T = 1 theta_mean^T + (s r)^T L^T: the accumulating
 		# NT product of the scaled draw (size x basis) with the lower-triangular factor
 		invV = self._invV_device()
-		dt = _lib.dtype_code(invV.dtype)
-		st = _lib.stream_ptr
 		Lc, _ = self._chol(invV, "V^-1 (sample_theta)")
-		_lib.check(lib.stpy_tril(dt, basis, _lib.ptr(Lc), _lib.ld(Lc), st()), "stpy_tril")
+		_lib.tril(Lc)
 		rt = (float(self.s) * random_vector).T.contiguous().to(device=Lc.device, dtype=Lc.dtype)          # (size, basis)
 		thT = torch.empty((size, basis), dtype=Lc.dtype, device=Lc.device)
 		thT.copy_(self._theta.reshape(1, basis).expand(size, basis))
-		_lib.check(lib.stpy_gemm_nt(dt, size, basis, basis, _lib.ptr(rt), _lib.ld(rt), _lib.ptr(Lc), _lib.ld(Lc), _lib.ptr(thT), _lib.ld(thT), 2, 0, st()), "stpy_gemm_nt")
+		_lib.gemm_nt(rt, Lc, thT, 2)
 		return thT
 
 	def sample_theta(self, size=1, prior=False):
@@ -588,17 +504,13 @@ class KernelizedFeatures(GaussianProcess):
 
 	def _features_times_theta(self, xtest, thT, out=None, mode=0):
 		"""Phi(xtest) theta, (M, size), device (``out`` given: accumulated per ``mode``)."""
-		lib = _lib.load()
 		xt = _lib.to_device(xtest, thT.dtype)
 		Phi = _lib.to_device(self.embedding.embed(xt), thT.dtype)
 		if Phi.stride(1) != 1:
 			Phi = Phi.contiguous()
-		M, m = Phi.shape
-		size = thT.shape[0]
 		if out is None:
-			out = torch.empty((M, size), dtype=thT.dtype, device=thT.device)
-		_lib.check(lib.stpy_gemm_nt(_lib.dtype_code(thT.dtype), M, size, m, _lib.ptr(Phi), _lib.ld(Phi), _lib.ptr(thT), _lib.ld(thT), _lib.ptr(out), _lib.ld(out), mode, 0,
-									_lib.stream_ptr()), "stpy_gemm_nt")
+			out = torch.empty((Phi.shape[0], thT.shape[0]), dtype=thT.dtype, device=thT.device)
+		_lib.gemm_nt(Phi, thT, out, mode)
 		return out
 
 	def sample(self, xtest, size=1, prior=False):
@@ -617,13 +529,10 @@ class KernelizedFeatures(GaussianProcess):
 		kernelized_features.py:300-317 (pathwise / Matheron update): a prior draw in feature space, corrected by the exact GP of
 		``kernel_object`` on the data:  f = Phi* theta + K* (K + s^2 lam I)^-1 (y - Phi theta).
 		"""
-		lib = _lib.load()
 		basis = self.get_basis_size()
 		random_vector = self._draw(basis, size)
 		xd = _lib.to_device(self.x)
 		dtype, dev = xd.dtype, xd.device
-		dt = _lib.dtype_code(dtype)
-		st = _lib.stream_ptr
 		thT = self._prior_theta_t(random_vector, dtype, dev)                                    # (size, basis)
 		xt = _lib.to_device(xtest, dtype)
 		N, M = xd.shape[0], xt.shape[0]
@@ -634,15 +543,15 @@ class KernelizedFeatures(GaussianProcess):
 		Phi = _lib.to_device(self.embedding.embed(xd), dtype)
 		if Phi.stride(1) != 1:
 			Phi = Phi.contiguous()
-		_lib.check(lib.stpy_gemm_nt(dt, size, N, basis, _lib.ptr(thT), _lib.ld(thT), _lib.ptr(Phi), _lib.ld(Phi), _lib.ptr(Rt), _lib.ld(Rt), 1, 0, st()), "stpy_gemm_nt")
+		_lib.gemm_nt(thT, Phi, Rt, 1)
 		del Phi
 		# K = k(x, x) + s^2 lam I -> Cholesky;  f += (K* L^-T) (R^T L^-T)^T
 		K = torch.empty((N, N), dtype=dtype, device=dev)
 		kernel_object._kernel_into(xd, xd, K, None, diag_add=float(self.s) ** 2 * float(self.lam), lower_only=True)
 		L, winv = self._chol(K, "k(x, x) + s^2 lam I (sample_matheron)")
-		_lib.check(lib.stpy_trsm_right_lt(dt, size, N, _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(Rt), _lib.ld(Rt), self.nb, 0, None, 0, st()), "stpy_trsm_right_lt")
+		_lib.trsm_right_lt(Rt, L, winv, self.nb)
 		X = torch.empty((M, N), dtype=dtype, device=dev)
 		kernel_object._kernel_into(xd, xt, X)                                                   # K* = k(x, xtest): (M, N)
-		_lib.check(lib.stpy_trsm_right_lt(dt, M, N, _lib.ptr(L), _lib.ld(L), _lib.ptr(winv), winv.numel(), _lib.ptr(X), _lib.ld(X), self.nb, 0, None, 0, st()), "stpy_trsm_right_lt")
-		_lib.check(lib.stpy_gemm_nt(dt, M, size, N, _lib.ptr(X), _lib.ld(X), _lib.ptr(Rt), _lib.ld(Rt), _lib.ptr(f), _lib.ld(f), 2, 0, st()), "stpy_gemm_nt")
+		_lib.trsm_right_lt(X, L, winv, self.nb)
+		_lib.gemm_nt(X, Rt, f, 2)
 		return _lib.like_input(f, xtest)

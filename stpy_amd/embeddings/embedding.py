@@ -78,21 +78,11 @@ class RFFEmbedding(Embedding):
 			self.bs = torch.from_numpy(self.bs)
 
 	def _embed_device(self, xd, transposed):
-		lib = _lib.load()
-		(times, d) = xd.shape
 		Wd = _lib.to_device(self.W, xd.dtype)
 		bd = _lib.to_device(self.b, xd.dtype) if self.biased == True else None
-		shape = (self.m, times) if transposed else (times, self.m)
-		out = torch.empty(shape, dtype=xd.dtype, device=xd.device)
 		scale = float(np.sqrt(2. / float(self.m)) * np.sqrt(self.kappa))
 		# (large fp32 d = 64 shapes: a workspace for the split W lets the contraction run on the bf16 matrix cores; 0 bytes otherwise)
-		wb = 0 if transposed else int(lib.stpy_rff_workspace_bytes(_lib.dtype_code(xd.dtype), times, d, self.m))
-		work = torch.empty((wb,), dtype=torch.uint8, device=xd.device) if wb > 0 else None
-		rc = lib.stpy_rff_embed(_lib.dtype_code(xd.dtype), _lib.ptr(xd), times, xd.stride(0), d, _lib.ptr(Wd), Wd.stride(0),
-								self.m, _lib.ptr(bd), None, scale, _lib.ptr(out), out.stride(0), 1 if transposed else 0,
-								_lib.ptr(work), wb, _lib.stream_ptr())
-		_lib.check(rc, "stpy_rff_embed")
-		return out
+		return _lib.rff_embed(xd, Wd, self.m, scale, bias=bd, transposed=transposed, workspace=not transposed)
 
 	def embed(self, x):
 		"""
@@ -178,15 +168,8 @@ class QuadratureEmbedding(Embedding):
 		return torch.cat([Wd, Wd]).contiguous(), torch.cat([amp, amp]), None
 
 	def _embed_device(self, xd, transposed):
-		lib = _lib.load()
-		times, d = xd.shape
-		Wd, amp, bias = self._operands(xd.dtype, d)
-		m = Wd.shape[0]
-		out = torch.empty((m, times) if transposed else (times, m), dtype=xd.dtype, device=xd.device)
-		rc = lib.stpy_rff_embed(_lib.dtype_code(xd.dtype), _lib.ptr(xd), times, xd.stride(0), d, _lib.ptr(Wd), Wd.stride(0), m,
-								_lib.ptr(bias), _lib.ptr(amp), float(np.sqrt(self.kappa)), _lib.ptr(out), out.stride(0), 1 if transposed else 0, None, 0, _lib.stream_ptr())
-		_lib.check(rc, "stpy_rff_embed")
-		return out
+		Wd, amp, bias = self._operands(xd.dtype, xd.shape[1])
+		return _lib.rff_embed(xd, Wd, Wd.shape[0], float(np.sqrt(self.kappa)), bias=bias, feat_scale=amp, transposed=transposed)
 
 	def embed(self, x):
 		"""embedding.py:450-466: (n, d) -> (n, m)."""

@@ -310,14 +310,11 @@ class KernelFunction:
 	def _run_items(self, items, a, b, out, diag_add=0.0, lower_only=False, first_is_set=True):
 		"""Evaluates a list of resolved items into ``out``.  The first one's operation is taken as "set" unless
 		``first_is_set`` is False (then ``out`` already holds a value the chain continues from)."""
-		lib = _lib.load()
 		if first_is_set and items and items[0]['op'] != "-":
 			items = [dict(items[0], op="-")] + list(items[1:])
-		dt = _lib.dtype_code(out.dtype)
-		n, q = a.shape[0], b.shape[0]
 		launches = self._plan(items)
 		dmax = max(len(l['term']['inv_ls']) for l in launches)
-		work = torch.empty((int(lib.stpy_gram_workspace_bytes(dt, n, q, dmax)),), dtype=torch.uint8, device=out.device)
+		work = _lib.gram_workspace(a.shape[0], b.shape[0], dmax, out)          # one scratch for every launch
 		tmp = None
 		same = a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride())
 		for idx, l in enumerate(launches):
@@ -329,33 +326,27 @@ class KernelFunction:
 			if t['premap'] is not None:
 				am = self._premap(a, t['group'], t['premap'])
 				bm = am if same else self._premap(b, t['group'], t['premap'])
-				cols, d_eff = None, am.shape[1]
+				cols = None
 			else:
-				am, bm, d_eff = a, b, len(t['group'])
+				am, bm = a, b
 				cols = None if t['group'] == list(range(a.shape[1])) else _dev_const(t['group'], None, out.device, int32=True)
 			inv_ls = _dev_const(t['inv_ls'], out.dtype, out.device)
-			rc = lib.stpy_gram(t['kind'], dt, _lib.ptr(am), n, am.stride(0), _lib.ptr(bm), q, bm.stride(0),
-							   d_eff, _lib.ptr(cols), _lib.ptr(inv_ls), t['kappa'], t['offset'],
-							   diag_add if (last and not l['fold']) else 0.0, 1 if lower_only else 0, l['combine'],
-							   _lib.ptr(target), target.stride(0), _lib.ptr(work), work.numel() * work.element_size(), _lib.stream_ptr())
-			_lib.check(rc, "stpy_gram")
+			_lib.gram(t['kind'], am, bm, target, inv_ls, cols, t['kappa'], t['offset'], diag_add=diag_add if (last and not l['fold']) else 0.0,
+					  lower_only=lower_only, combine=l['combine'], work=work)
 			if l['fold']:       # out *= (sum of the item's terms), then the noise term if this was the last launch
-				_lib.check(lib.stpy_combine(dt, q, n, _lib.ptr(out), out.stride(0), _lib.ptr(tmp), tmp.stride(0), _lib.OUT_MUL,
-											diag_add if last else 0.0, _lib.stream_ptr()), "stpy_combine")
+				_lib.combine(out, tmp, _lib.OUT_MUL, diag_add if last else 0.0)
 		return out
 
 	@staticmethod
 	def _premap(x, group, cov):
 		"""x[:, group] @ cov on the device (kernels.py:487-490) through the NT product: B = cov^T."""
-		lib = _lib.load()
 		xg = x if group == list(range(x.shape[1])) else x[:, group]
 		xg = xg.contiguous()
 		ct = cov.to(device=x.device, dtype=x.dtype).t().contiguous()
 		if ct.shape[1] != xg.shape[1]:
 			raise ValueError("full-covariance kernel: cov has %d rows for %d selected columns" % (ct.shape[1], xg.shape[1]))
 		out = torch.empty((xg.shape[0], ct.shape[0]), dtype=x.dtype, device=x.device)
-		_lib.check(lib.stpy_gemm_nt(_lib.dtype_code(x.dtype), xg.shape[0], ct.shape[0], xg.shape[1], _lib.ptr(xg), xg.stride(0),
-									_lib.ptr(ct), ct.stride(0), _lib.ptr(out), out.stride(0), 0, 0, _lib.stream_ptr()), "stpy_gemm_nt")
+		_lib.gemm_nt(xg, ct, out)
 		return out
 
 	def kernel(self, a, b, **kwargs):
@@ -367,12 +358,10 @@ class KernelFunction:
 		return _lib.like_input(out, a)
 
 	def _diag_into(self, x, out, kwargs=None, items=None):
-		lib = _lib.load()
 		if items is None:
 			items = self._resolve(dict(kwargs) if kwargs else {})
 		elif items and items[0]['op'] != "-":
 			items = [dict(items[0], op="-")] + list(items[1:])
-		dt = _lib.dtype_code(out.dtype)
 		tmp = None
 		for l in self._plan(items):
 			t = l['term']
@@ -381,15 +370,11 @@ class KernelFunction:
 			target = tmp if l['target'] == "tmp" else out
 			# (a mapped stationary kernel has k(x, x) = kappa whatever the map; only dot-product kernels read x)
 			group = t['group'] if t['premap'] is None else list(range(x.shape[1]))
-			d_eff = len(group) if t['premap'] is None else 0
 			cols = None if group == list(range(x.shape[1])) else _dev_const(group, None, out.device, int32=True)
 			inv_ls = _dev_const(t['inv_ls'], out.dtype, out.device)
-			rc = lib.stpy_gram_diag(t['kind'], dt, _lib.ptr(x), x.shape[0], x.stride(0), d_eff, _lib.ptr(cols),
-									_lib.ptr(inv_ls), t['kappa'], t['offset'], l['combine'], _lib.ptr(target), _lib.stream_ptr())
-			_lib.check(rc, "stpy_gram_diag")
+			_lib.gram_diag(t['kind'], x, target, inv_ls, cols, t['kappa'], t['offset'], l['combine'], d=None if t['premap'] is None else 0)
 			if l['fold']:
-				_lib.check(lib.stpy_combine(dt, 1, out.shape[0], _lib.ptr(out), out.shape[0], _lib.ptr(tmp), tmp.shape[0], _lib.OUT_MUL, 0.0,
-											_lib.stream_ptr()), "stpy_combine")
+				_lib.combine(out.reshape(1, -1), tmp.reshape(1, -1), _lib.OUT_MUL)
 		return out
 
 	def kernel_self_diag(self, x, **kwargs):
@@ -428,11 +413,9 @@ class KernelFunction:
 		(G[:, group] += G_z cov^T, one stpy_gemm_nt); the factors of a * item enter through the coefficients:
 		C o prod_{l != j} K_l, formed with stpy_gram's multiply combine.
 		"""
-		lib = _lib.load()
 		items = self._resolve(dict(kwargs) if kwargs else {})
 		if items and items[0]['op'] != "-":
 			items = [dict(items[0], op="-")] + list(items[1:])
-		order = 1 if H is None else 2
 		if H is not None:
 			for it in items:
 				if it['op'] == "*":
@@ -446,7 +429,6 @@ class KernelFunction:
 		m, n = xt.shape[0], x.shape[0]
 		if m == 0 or n == 0:
 			return G
-		dt = _lib.dtype_code(G.dtype)
 		dev = G.device
 		has_mul = any(it['op'] == "*" for it in items)
 		C = None
@@ -466,22 +448,19 @@ class KernelFunction:
 						continue
 					tmp = torch.empty((m, n), dtype=G.dtype, device=dev)
 					self._run_items(fac, x, xt, tmp)
-					_lib.check(lib.stpy_combine(dt, m, n, _lib.ptr(Ci), Ci.stride(0), _lib.ptr(tmp), tmp.stride(0), _lib.OUT_MUL, 0.0,
-												_lib.stream_ptr()), "stpy_combine")
-				coef = (None, None, Ci, None)
+					_lib.combine(Ci, tmp, _lib.OUT_MUL)
+				coef = dict(Wt=Ci)
 			elif has_mul:
-				coef = (None, None, C, None)
+				coef = dict(Wt=C)
 			else:
-				coef = (alpha, u, Wt, v)
+				coef = dict(alpha=alpha, u=u, Wt=Wt, v=v)
 			for t in it['terms']:
-				self._term_grad(t, x, xt, coef, G, H, order)
+				self._term_grad(t, x, xt, coef, G, H)
 		return G
 
-	def _term_grad(self, t, x, xt, coef, G, H, order):
-		lib = _lib.load()
-		alpha, u, Wt, v = coef
-		m, n = xt.shape[0], x.shape[0]
-		dt = _lib.dtype_code(G.dtype)
+	def _term_grad(self, t, x, xt, coef, G, H):
+		"""One stpy_gram_grad launch of term t into G (H); coef: the alpha / u / Wt / v keywords of _lib.gram_grad."""
+		m = xt.shape[0]
 		dev = G.device
 		if t['premap'] is not None:
 			group = t['group']
@@ -490,11 +469,10 @@ class KernelFunction:
 			p = zx.shape[1]
 			Gz = torch.empty((m, p), dtype=G.dtype, device=dev)
 			Hz = torch.empty((m, p, p), dtype=G.dtype, device=dev) if H is not None else None
-			self._launch_grad(t['kind'], zx, zt, p, None, [1.0] * p, t['kappa'], t['offset'], coef, _lib.OUT_SET, Gz, Hz, order)
+			_lib.gram_grad(t['kind'], zx, zt, Gz, _dev_const([1.0] * p, G.dtype, dev), None, t['kappa'], t['offset'], combine=_lib.OUT_SET, H=Hz, **coef)
 			cov = t['premap'].to(device=dev, dtype=G.dtype).contiguous()            # (dg, p): G_z cov^T is the NT product of G_z and cov
 			Gx = torch.empty((m, cov.shape[0]), dtype=G.dtype, device=dev)
-			_lib.check(lib.stpy_gemm_nt(dt, m, cov.shape[0], p, _lib.ptr(Gz), Gz.stride(0), _lib.ptr(cov), cov.stride(0), _lib.ptr(Gx), Gx.stride(0),
-										0, 0, _lib.stream_ptr()), "stpy_gemm_nt")
+			_lib.gemm_nt(Gz, cov, Gx)
 			gi = torch.as_tensor(group, dtype=torch.long, device=dev)
 			G.index_add_(1, gi, Gx)
 			if H is not None:                   # cov H_z cov^T per point (d x d, single points): small, plumbing
@@ -503,20 +481,7 @@ class KernelFunction:
 			return
 		group = t['group']
 		cols = None if group == list(range(x.shape[1])) else _dev_const(group, None, dev, int32=True)
-		self._launch_grad(t['kind'], x, xt, len(group), cols, t['inv_ls'], t['kappa'], t['offset'], coef, _lib.OUT_ADD, G, H, order)
-
-	@staticmethod
-	def _launch_grad(kind, x, xt, d, cols, inv_ls, kappa, offset, coef, combine, G, H, order):
-		lib = _lib.load()
-		alpha, u, Wt, v = coef
-		m, n = xt.shape[0], x.shape[0]
-		dt = _lib.dtype_code(G.dtype)
-		il = _dev_const(inv_ls, G.dtype, G.device)
-		work = torch.empty((int(lib.stpy_gram_grad_workspace_bytes(dt, m, n, d, order)),), dtype=torch.uint8, device=G.device)
-		rc = lib.stpy_gram_grad(kind, dt, _lib.ptr(x), n, x.stride(0), _lib.ptr(xt), m, xt.stride(0), d, _lib.ptr(cols), _lib.ptr(il),
-								float(kappa), float(offset), _lib.ptr(alpha), _lib.ptr(u), _lib.ptr(Wt), Wt.stride(0) if Wt is not None else 0,
-								_lib.ptr(v), order, combine, _lib.ptr(G), G.stride(0), _lib.ptr(H), _lib.ptr(work), work.numel(), _lib.stream_ptr())
-		_lib.check(rc, "stpy_gram_grad")
+		_lib.gram_grad(t['kind'], x, xt, G, _dev_const(t['inv_ls'], G.dtype, dev), cols, t['kappa'], t['offset'], combine=_lib.OUT_ADD, H=H, **coef)
 
 	def _self_grad_into(self, xt, coef, G, kwargs=None):
 		"""G[t] += coef_t * grad_x k(x, x) at x = xt_t: zero for stationary terms (k(x, x) = kappa); for the dot-product terms

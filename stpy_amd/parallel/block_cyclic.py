@@ -76,10 +76,8 @@ class HipLocalOps:
 	"""Local tile arithmetic on this process's GPU through libstpy_hip.  No CPU path."""
 
 	def __init__(self, dtype=torch.float64, nb=0):
-		self.lib = _lib.load()
 		self.device = _lib.device()
 		self.dtype = dtype
-		self.code = _lib.dtype_code(dtype)
 		self.nb = nb
 		self.flags = 0
 		self._skwork = {}
@@ -116,8 +114,7 @@ class HipLocalOps:
 
 	def add_into(self, out, src):
 		"""out += src on (strided) 2-D views."""
-		_lib.check(self.lib.stpy_combine(self.code, out.shape[0], out.shape[1], _lib.ptr(out), out.stride(0), _lib.ptr(src), src.stride(0),
-										 _lib.OUT_ADD, 0.0, _lib.stream_ptr()), "stpy_combine")
+		_lib.combine(out, src, _lib.OUT_ADD)
 
 	def kdiag(self, kernel_object, xt):
 		out = self.empty(xt.shape[0])
@@ -126,20 +123,12 @@ class HipLocalOps:
 
 	def potrf(self, A):
 		"""In-place Cholesky of the (strided) square view A; returns (winv, info_tensor)."""
-		n = A.shape[0]
-		winv = self.empty(int(self.lib.stpy_potrf_winv_elems(n)))
-		work = torch.empty((int(self.lib.stpy_potrf_workspace_bytes(self.code, n, self.nb)),), dtype=torch.uint8, device=self.device)
-		info = torch.zeros((1,), dtype=torch.int32, device=self.device)
-		_lib.check(self.lib.stpy_potrf(self.code, n, _lib.ptr(A), A.stride(0), _lib.ptr(winv), winv.numel(), _lib.ptr(work), work.numel() * work.element_size(), self.nb, self.flags, _lib.ptr(info), _lib.stream_ptr()), "stpy_potrf")
-		return winv, info
+		return _lib.potrf(A, self.nb, self.flags)
 
 	def trsm_right_lt(self, B, L, winv):
 		"""B <- B L^-T in place; B: (m, n) strided view, L: (n, n) view, winv from potrf(L)."""
-		m, n = B.shape
-		if m == 0:
-			return
-		_lib.check(self.lib.stpy_trsm_right_lt(self.code, m, n, _lib.ptr(L), L.stride(0), _lib.ptr(winv), winv.numel(), _lib.ptr(B), B.stride(0),
-											   self.nb, self.flags, None, 0, _lib.stream_ptr()), "stpy_trsm_right_lt")
+		if B.shape[0] > 0:
+			_lib.trsm_right_lt(B, L, winv, self.nb, self.flags)
 
 	def gemm_nt(self, A, B, C, mode, bc=None):
 		"""C (mode 0: =, 1: -=) A B^T.  bc = (nb_dist, pr, pc, myr, myc, i0, j0) enables the staircase."""
@@ -147,23 +136,20 @@ class HipLocalOps:
 		n = B.shape[0]
 		if m == 0 or n == 0 or k == 0:
 			return
-		if bc is None:
-			passes = int(self.lib.stpy_gemm_nt_splitk_passes(m, n, k))
-			if passes > 1:        # few output tiles, long K (partial sums of the distributed solve)
-				# one workspace per stream, grown on demand and kept: no allocation inside the per-block loop
-				key = torch.cuda.current_stream().cuda_stream
-				work = self._skwork.get(key)
-				if work is None or work.numel() < passes * m * n:
-					work = self._skwork[key] = self.empty(passes * m * n)
-				_lib.check(self.lib.stpy_gemm_nt_splitk(self.code, m, n, k, _lib.ptr(A), A.stride(0), _lib.ptr(B), B.stride(0), _lib.ptr(C), C.stride(0),
-														mode, passes, _lib.ptr(work), work.numel() * work.element_size(), _lib.stream_ptr()), "stpy_gemm_nt_splitk")
-				return
-			rc = self.lib.stpy_gemm_nt(self.code, m, n, k, _lib.ptr(A), A.stride(0), _lib.ptr(B), B.stride(0), _lib.ptr(C), C.stride(0),
-									   mode, 0, _lib.stream_ptr())
-		else:
-			rc = self.lib.stpy_gemm_nt_bc(self.code, m, n, k, _lib.ptr(A), A.stride(0), _lib.ptr(B), B.stride(0), _lib.ptr(C), C.stride(0),
-										  mode, *[int(v) for v in bc], _lib.stream_ptr())
-		_lib.check(rc, "stpy_gemm_nt")
+		if bc is not None:
+			_lib.gemm_nt_bc(A, B, C, mode, bc)
+			return
+		passes = _lib.gemm_nt_splitk_passes(A, B)
+		if passes <= 1:
+			_lib.gemm_nt(A, B, C, mode)
+			return
+		# few output tiles, long K (partial sums of the distributed solve)
+		# one workspace per stream, grown on demand and kept: no allocation inside the per-block loop
+		key = torch.cuda.current_stream().cuda_stream
+		work = self._skwork.get(key)
+		if work is None or work.numel() < passes * m * n:
+			work = self._skwork[key] = self.empty(passes * m * n)
+		_lib.gemm_nt_splitk(A, B, C, mode, passes, work)
 
 	def row_sums(self, X, z, out=None):
 		"""(sum_k X[i,k] z[k], sum_k X[i,k]^2) for every row of the strided view X; ``out``: a contiguous (2, m) buffer."""
@@ -174,22 +160,18 @@ class HipLocalOps:
 		if n == 0:
 			out.zero_()
 			return s1, s2
-		_lib.check(self.lib.stpy_predict(self.code, m, n, _lib.ptr(X), X.stride(0), _lib.ptr(z), None, _lib.ptr(s1), _lib.ptr(s2), 2,
-										 _lib.stream_ptr()), "stpy_predict")
+		_lib.predict(X, z, s1, s2, clamp=2)
 		return s1, s2
 
 	def predict_finish(self, mu, sumsq, kdiag, scale, clamp, want_sigma=True):
 		"""mu *= scale (in place); sigma = sqrt(kdiag - scale * sumsq): the epilogue after the all-reduce of the partial sums."""
 		sigma = self.empty(mu.shape[0]) if want_sigma else None
-		_lib.check(self.lib.stpy_predict_finish(self.code, mu.shape[0], _lib.ptr(mu), _lib.ptr(sumsq), _lib.ptr(kdiag), float(scale), _lib.ptr(sigma),
-												1 if clamp else 0, _lib.stream_ptr()), "stpy_predict_finish")
+		_lib.predict_finish(mu, sumsq, kdiag, float(scale), sigma, 1 if clamp else 0)
 		return mu, sigma
 
 	def logdet(self, L):
 		"""sum_i log L_ii of the (strided) factor block L."""
-		out2 = self.empty(2)
-		_lib.check(self.lib.stpy_logdet_quad(self.code, L.shape[0], _lib.ptr(L), L.stride(0), None, _lib.ptr(out2), _lib.stream_ptr()), "stpy_logdet_quad")
-		return out2[0]
+		return _lib.logdet_quad(L)[0]
 
 
 class _Factor:

@@ -58,6 +58,18 @@ def test_product_does_not_import_oracle():
 				assert "/root/reference" not in src
 
 
+def test_only_lib_calls_the_library():
+	"""The C ABI's calling convention lives in stpy_amd/_lib.py: every other module launches through its typed wrappers and names no
+	library symbol (``lib.stpy_*``)."""
+	pkg = os.path.join(ROOT, "stpy_amd")
+	for dirpath, _, files in os.walk(pkg):
+		for f in files:
+			path = os.path.join(dirpath, f)
+			if f.endswith(".py") and os.path.relpath(path, pkg) != "_lib.py":
+				hits = re.findall(r"\.\s*stpy_\w+", open(path).read())
+				assert not hits, "%s calls the library directly: %s" % (os.path.relpath(path, ROOT), hits)
+
+
 @pytest.mark.parametrize("src", ["gemm.hip", "potrf.hip"])
 def test_mfma_kernels_stay_in_registers(src, tmp_path):
 	out = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-c", os.path.join(CSRC, src),
