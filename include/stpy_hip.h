@@ -334,6 +334,31 @@ int stpy_rff_embed(int dtype, const void* x, int64_t n, int64_t ldx, int d,
                    void* out, int64_t ldo, int transposed, void* work, int64_t work_bytes, void* stream);
 
 /*
+ * Input gradients of a Fourier-feature expansion (QuadratureEmbedding.derivative_1 / derivative_2, embedding.py:268-304, contracted
+ * with coefficients; the autograd of KernelizedFeatures.mean_std through a test tensor; sample_and_optimize,
+ * kernelized_features.py:501-535).  The feature map is exactly that of stpy_rff_embed (x, W, bias, feat_scale, scale: same meaning,
+ * same layout rules; an odd m with a bias only):  phi_tj = a_j cos(<W_j, x_t> + bias_j), or a_j cos | a_j sin of <W_j, x_t> for
+ * j < m/2 | j >= m/2 without a bias, a_j = scale * feat_scale[j].  With coefficients C (n x m, ldc >= m; ldc == 0: ONE row of m
+ * elements shared by all points -- a sampled theta):
+ *   val[t]                    (op)= sum_j C_tj phi_tj                          (n elements; val may be NULL)
+ *   G[t*ldg + k]              (op)= sum_j C_tj d phi_tj / d x_tk               = sum_j C_tj a_j (-sin | cos)(.) W_jk
+ *   order 2 also: H[(t*ldg + k)*ldg + l] (op)= sum_j C_tj d^2 phi_tj / d x_tk d x_tl = -sum_j C_tj phi_tj W_jk W_jl
+ *                                                                              (n blocks of ldg x ldg, the layout of stpy_gram_grad)
+ * i.e. G = (C o Phi') W in one pass: neither Phi, Phi' nor the (d, m, n) Jacobian is stored.  combine: STPY_OUT_SET or STPY_OUT_ADD
+ * (the parts of a concatenated embedding accumulate).  fp64 uses libm sin / cos, fp32 the hardware functions of the embed's GEMM
+ * epilogue, so val agrees with stpy_rff_embed followed by a dot product to rounding.  The feature range is split into chunks whose
+ * partial sums land in `work` (stpy_rff_grad_workspace_bytes(dtype, n, d, m, order) bytes; NULL -20, undersized -21) and are added in
+ * a fixed order: results are bit-identical from run to run.  Refused: dtype (-1), NULL x / W / C / G (-2 / -6 / -12 / -17), d <= 0
+ * (-5), ldx / ldw / ldg < d (-4 / -7 / -18), an odd m without a bias (-8), 0 < ldc < m (-13), order (-14), combine (-15), order 2
+ * without H (-19).  n == 0 or m == 0: nothing is written.
+ */
+int64_t stpy_rff_grad_workspace_bytes(int dtype, int64_t n, int d, int64_t m, int order);
+int stpy_rff_grad(int dtype, const void* x, int64_t n, int64_t ldx, int d,
+                  const void* W, int64_t ldw, int64_t m, const void* bias, const void* feat_scale, double scale,
+                  const void* C, int64_t ldc, int order, int combine, void* val, void* G, int64_t ldg, void* H,
+                  void* work, int64_t work_bytes, void* stream);
+
+/*
  * Launch profiler (bench.py's live roofline numbers).  While enabled, HIP events are recorded on
  * the launch stream around every MFMA GEMM / diagonal-block launch.  tag: 0 = trailing SYRK
  * update of potrf, 1 = panel GEMMs of potrf, 2 = GEMMs of stpy_trsm_right_lt, 3 = 128x128

@@ -66,6 +66,8 @@ SIGNATURES = {
 	"stpy_trsm_right_ln": (_i32, [_i32, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
 	"stpy_rff_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_rff_embed": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _dbl, _vp, _i64, _i32, _vp, _i64, _vp]),
+	"stpy_rff_grad_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64, _i32]),
+	"stpy_rff_grad": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _dbl, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_profile_enable": (None, [_i32]),
 	"stpy_async_status": (_i32, [_vp]),
 	"stpy_profile_read_union": (_i32, [_i32, _c.POINTER(_dbl), _c.POINTER(_dbl), _c.POINTER(_i64)]),
@@ -393,3 +395,15 @@ def rff_embed(x, W, m, scale, bias=None, feat_scale=None, transposed=False, work
 	_launch("stpy_rff_embed", dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(W), ld(W), m, ptr(bias), ptr(feat_scale), scale, ptr(out), ld(out),
 			int(transposed), ptr(work), wb)
 	return out
+
+
+def rff_grad(x, W, m, scale, C, G, bias=None, feat_scale=None, val=None, H=None, combine=OUT_SET):
+	"""G[t] (combine)= d/dx_t sum_j C[t, j] phi_j(x_t) for the feature map of rff_embed (same W, m, scale, bias, feat_scale);
+	``val`` (n,) also receives the sums themselves and ``H`` (n, ld(G), ld(G)) their Hessians.  C: (n, m) rows, may be a column
+	window of a wider matrix, or ONE row (a 1-D tensor of m elements) shared by all points."""
+	n, d = x.shape
+	order = 1 if H is None else 2
+	ldc = 0 if C.dim() == 1 else ld(C)
+	work = _work(max(int(load().stpy_rff_grad_workspace_bytes(dtype_code(x.dtype), n, d, m, order)), 1), x)
+	_launch("stpy_rff_grad", dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(W), ld(W), m, ptr(bias), ptr(feat_scale), float(scale), ptr(C), ldc,
+			order, combine, ptr(val), ptr(G), ld(G), ptr(H), ptr(work), work.numel())

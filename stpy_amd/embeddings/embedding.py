@@ -4,6 +4,11 @@ Drop-in for ``stpy.embeddings.embedding.{Embedding, RFFEmbedding, QuadratureEmbe
 node / weight rules).  ``embed`` runs in ``stpy_rff_embed`` (csrc/rff.hip); weight sampling (RFF: global numpy RNG)
 and the quadrature node / weight tables (a few hundred numbers) stay on the host exactly as in the reference, and
 ``W`` / ``b`` / ``weights`` may be injected.
+
+Input gradients (embedding.py:268-304 ``derivative_1`` / ``derivative_2``): every Fourier embedding describes its device operands
+once (``_operands``: W, bias, per-feature amplitudes, scale), and both ``embed`` and ``value_grad`` -- value, gradient and Hessian
+of ``sum_j C_tj phi_j(x_t)`` in one ``stpy_rff_grad`` launch (csrc/rffgrad.hip), without the (d, m, n) Jacobian -- read that
+description.  ``ConcatEmbedding`` accumulates its parts over their coefficient columns.
 """
 import numpy as np
 import torch
@@ -41,6 +46,29 @@ class Embedding():
 	def get_m(self):
 		return self.m
 
+	def _operands(self, dtype, d):
+		"""(W, bias, feat_scale, scale): the device operands of ``stpy_rff_embed`` / ``stpy_rff_grad`` for inputs of d columns; the
+		feature count is W.shape[0].  The ONE description of the feature map that ``embed`` and the input gradients share."""
+		raise NotImplementedError("%s has no device description of its feature map (no input gradients)" % type(self).__name__)
+
+	def _grad_device(self, xd, C, G, val=None, H=None, combine=_lib.OUT_SET):
+		"""stpy_rff_grad on device tensors: G (n, d) (combine)= d/dx sum_j C_tj phi_j(x_t), ``val`` (n,) the sums, ``H`` (n, d, d) their
+		Hessians.  C: (n, m) coefficient rows (may be a column window of a wider matrix) or one shared row (m,)."""
+		W, bias, fs, scale = self._operands(xd.dtype, xd.shape[1])
+		_lib.rff_grad(xd, W, W.shape[0], scale, C, G, bias=bias, feat_scale=fs, val=val, H=H, combine=combine)
+
+	def value_grad(self, x, C, hessian=False):
+		"""(val (n,), G (n, d)[, H (n, d, d)]) of f_t(x) = sum_j C_tj phi_j(x) at the rows of x, on the device: one
+		``stpy_rff_grad`` launch, the (d, m, n) Jacobian of the embedding is never formed.  C: (n, m), or (m,) shared by all rows."""
+		xd = _lib.to_device(x)
+		Cd = _lib.to_device(C, xd.dtype)
+		n, d = xd.shape
+		val = torch.empty((n,), dtype=xd.dtype, device=xd.device)
+		G = torch.empty((n, d), dtype=xd.dtype, device=xd.device)
+		H = torch.empty((n, d, d), dtype=xd.dtype, device=xd.device) if hessian else None
+		self._grad_device(xd, Cd, G, val=val, H=H)
+		return (val, G, H) if hessian else (val, G)
+
 
 class RFFEmbedding(Embedding):
 	"""Random Fourier features, embedding.py:139-241."""
@@ -77,10 +105,13 @@ class RFFEmbedding(Embedding):
 			self.b = torch.from_numpy(self.b)
 			self.bs = torch.from_numpy(self.bs)
 
+	def _operands(self, dtype, d):
+		Wd = _lib.to_device(self.W, dtype)[:self.m]
+		bd = _lib.to_device(self.b, dtype) if self.biased == True else None
+		return Wd, bd, None, float(np.sqrt(2. / float(self.m)) * np.sqrt(self.kappa))
+
 	def _embed_device(self, xd, transposed):
-		Wd = _lib.to_device(self.W, xd.dtype)
-		bd = _lib.to_device(self.b, xd.dtype) if self.biased == True else None
-		scale = float(np.sqrt(2. / float(self.m)) * np.sqrt(self.kappa))
+		Wd, bd, _, scale = self._operands(xd.dtype, xd.shape[1])
 		# (large fp32 d = 64 shapes: a workspace for the split W lets the contraction run on the bf16 matrix cores; 0 bytes otherwise)
 		return _lib.rff_embed(xd, Wd, self.m, scale, bias=bd, transposed=transposed, workspace=not transposed)
 
@@ -160,16 +191,52 @@ class QuadratureEmbedding(Embedding):
 			self.m = self.m * 2
 
 	def _operands(self, dtype, d):
-		"""(frequency rows, amplitudes, bias) of the device call for this embedding."""
+		"""(frequency rows stacked twice, bias, amplitudes sqrt(w_j), sqrt(kappa)) of the device calls for this embedding."""
 		Wd = _lib.to_device(self.W, dtype)[:, :d]
 		amp = torch.sqrt(_lib.to_device(self.weights, dtype).reshape(-1))
+		scale = float(np.sqrt(self.kappa))
 		if self.cosine:          # all-cosine: the biased form of the kernel with a zero phase
-			return Wd.contiguous(), amp, torch.zeros_like(amp)
-		return torch.cat([Wd, Wd]).contiguous(), torch.cat([amp, amp]), None
+			return Wd.contiguous(), torch.zeros_like(amp), amp, scale
+		return torch.cat([Wd, Wd]).contiguous(), None, torch.cat([amp, amp]), scale
 
 	def _embed_device(self, xd, transposed):
-		Wd, amp, bias = self._operands(xd.dtype, xd.shape[1])
-		return _lib.rff_embed(xd, Wd, Wd.shape[0], float(np.sqrt(self.kappa)), bias=bias, feat_scale=amp, transposed=transposed)
+		Wd, bias, amp, scale = self._operands(xd.dtype, xd.shape[1])
+		return _lib.rff_embed(xd, Wd, Wd.shape[0], scale, bias=bias, feat_scale=amp, transposed=transposed)
+
+	def _derivative_planes(self, x, order):
+		"""The full Jacobian (order 1: (d, m, n)) or second-derivative tensor (order 2: (d, d, m, n)) of the embedding, one
+		transposed ``stpy_rff_embed`` per coordinate (pair): d phi_j / d x_k = sqrt(kappa) [sqrt(w_j) W_jk] cos(<W_j, x> + pi/2 | 0)
+		and d2 phi_j / d x_k d x_l = sqrt(kappa) [-sqrt(w_j) W_jk W_jl] cos(<W_j, x> + 0 | -pi/2) on the cos | sin halves, i.e. the
+		embed kernel with the bracket as per-feature amplitude and the phase as bias.  Small-problem convenience by contract: the
+		result has d (d^2) times the size of the embedding; the contraction with coefficients is ``value_grad``."""
+		if self.cosine:
+			raise NotImplementedError("Cosine only features derivative not implemented")
+		xd = _lib.to_device(x)
+		n, d = xd.shape
+		Wd, _, amp, scale = self._operands(xd.dtype, d)
+		m, half = Wd.shape[0], Wd.shape[0] // 2
+		bias = torch.zeros((m,), dtype=xd.dtype, device=xd.device)
+		if order == 1:
+			bias[:half] = np.pi / 2.          # cos(q + pi/2) = -sin(q)
+		else:
+			bias[half:] = -np.pi / 2.         # cos(q - pi/2) = sin(q)
+		planes = []
+		for k in range(d):
+			fk = amp * Wd[:, k]
+			if order == 1:
+				planes.append(_lib.rff_embed(xd, Wd, m, scale, bias=bias, feat_scale=fk.contiguous(), transposed=True))
+			else:
+				planes.append(torch.stack([_lib.rff_embed(xd, Wd, m, scale, bias=bias, feat_scale=(-fk * Wd[:, l]).contiguous(), transposed=True)
+										   for l in range(d)]))
+		return _lib.like_input(torch.stack(planes), x)
+
+	def derivative_1(self, x):
+		"""embedding.py:268-285: (d, m, n), z[k, j, t] = d phi_j(x_t) / d x_k."""
+		return self._derivative_planes(x, 1)
+
+	def derivative_2(self, x):
+		"""embedding.py:287-304: (d, d, m, n), z[k, l, j, t] = d2 phi_j(x_t) / d x_k d x_l."""
+		return self._derivative_planes(x, 2)
 
 	def embed(self, x):
 		"""embedding.py:450-466: (n, d) -> (n, m)."""
@@ -280,3 +347,12 @@ class ConcatEmbedding(Embedding):
 
 	def embed(self, xtest):
 		return torch.hstack([emb.embed(xtest) for emb in self.embeddings])
+
+	def _grad_device(self, xd, C, G, val=None, H=None, combine=_lib.OUT_SET):
+		"""The parts' contributions over their own coefficient columns, accumulated into the same outputs (STPY_OUT_ADD)."""
+		off = 0
+		for emb in self.embeddings:
+			mi = emb.get_m()
+			emb._grad_device(xd, C[off:off + mi] if C.dim() == 1 else C[:, off:off + mi], G, val=val, H=H, combine=combine)
+			combine = _lib.OUT_ADD
+			off += mi

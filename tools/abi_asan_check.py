@@ -16,7 +16,7 @@ import textwrap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "stpy_amd", "csrc")
-SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce", "grad", "append"]
+SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce", "grad", "append", "rffgrad"]
 
 CHILD = r'''
 import ctypes, sys
@@ -125,6 +125,28 @@ neg(lib.stpy_rff_embed(1, N, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 0, N, 0, N), "r
 neg(lib.stpy_rff_embed(1, P, 16, 2, 4, P, 4, 8, N, N, 1.0, P, 8, 0, N, 0, N), "rff ldx < d")
 neg(lib.stpy_rff_embed(1, P, 262144, 64, 64, P, 64, 32768, N, N, 1.0, P, 32768, 0, P, 16, N), "rff undersized workspace")
 zero(lib.stpy_rff_embed(1, N, 0, 4, 4, N, 4, 8, N, N, 1.0, N, 8, 0, N, 0, N), "rff empty")
+# ---- input gradients of the feature expansion (argument order: dtype, x, n, ldx, d, W, ldw, m, bias, feat_scale, scale, C, ldc, order, combine,
+# ---- val, G, ldg, H, work, work_bytes, stream)
+assert lib.stpy_rff_grad_workspace_bytes(0, 25, 4, 32768, 1) > 0 and lib.stpy_rff_grad_workspace_bytes(0, 0, 4, 64, 1) == 0
+assert lib.stpy_rff_grad_workspace_bytes(1, 4096, 64, 8192, 2) * 2 == lib.stpy_rff_grad_workspace_bytes(0, 4096, 64, 8192, 2)
+neg(lib.stpy_rff_grad(7, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad unknown dtype")
+neg(lib.stpy_rff_grad(0, N, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad null x")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 0, P, 4, 8, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad d = 0")
+neg(lib.stpy_rff_grad(0, P, 16, 2, 4, P, 4, 8, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad ldx < d")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, N, 4, 8, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad null W")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 2, 8, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad ldw < d")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 7, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad odd m without a bias")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, N, 8, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad null C")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 5, 1, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad 0 < ldc < m")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 3, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad order 3")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 1, 2, N, P, 4, N, P, 1 << 20, N), "rff_grad combine MUL")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 1, 0, N, N, 4, N, P, 1 << 20, N), "rff_grad null G")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 1, 0, N, P, 2, N, P, 1 << 20, N), "rff_grad ldg < d")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 2, 0, N, P, 4, N, P, 1 << 20, N), "rff_grad order 2 without H")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 0, 1, 0, N, P, 4, N, N, 0, N), "rff_grad null workspace (shared row)")
+neg(lib.stpy_rff_grad(0, P, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 1, 0, N, P, 4, N, P, 8, N), "rff_grad undersized workspace")
+zero(lib.stpy_rff_grad(0, N, 0, 4, 4, N, 4, 8, N, N, 1.0, N, 8, 1, 0, N, N, 4, N, N, 0, N), "rff_grad no points")
+zero(lib.stpy_rff_grad(0, N, 16, 4, 4, N, 4, 0, N, N, 1.0, N, 0, 1, 0, N, N, 4, N, N, 0, N), "rff_grad no features")
 # ---- switches and profiler (no device needed)
 for key in (5, 8, 9, 16, 17, 26, 28, 30, 32):
     v = lib.stpy_tune_get(key); assert v >= 0; lib.stpy_tune(key, v)
