@@ -88,6 +88,14 @@ const char* stpy_last_error_string(void);
  * work: NULL, or stpy_gram_workspace_bytes(dtype, n, q, d) bytes of scratch.  With a workspace the
  * inner products run on the MFMA contraction with the kernel function fused into its epilogue
  * (all kinds except MATERN12, which always uses the direct-difference tile kernel).
+ * Accuracy.  SE on every route, and MATERN32 / MATERN52 with a workspace, form r^2 = |a'|^2 + |b'|^2 - 2 <a', b'> from the points taken
+ * relative to the first row of `a` (a' = (a_i - a_0)[cols] * inv_ls, b' likewise: one common shift per call, read on the device), which
+ * a stationary kernel does not see.  The error of such an entry is proportional to the squared DIAMETER of the scaled data, not to its
+ * distance from the origin:  |out - exact| <= kappa (c 4 (d + 3) eps D^2 + 8 eps),  D^2 the largest scaled squared distance between two
+ * points of a and b, eps the machine epsilon of `dtype`, c = max |d phi / d r^2| = 1/2 (SE), 3/2 (MATERN32), 5/6 (MATERN52).  fp32 on
+ * data much wider than the lengthscale loses digits accordingly (about 4e-4 at a scaled diameter of 36).  The direct-difference routes
+ * (MATERN12 always, MATERN32 / MATERN52 without a workspace) are good to kappa (d + 8) eps wherever the data lies, and give kappa
+ * exactly on coincident points.  LINEAR and POLY are not translation invariant and are evaluated as written.
  */
 int64_t stpy_gram_workspace_bytes(int dtype, int64_t n, int64_t q, int d);
 int stpy_gram(int kind, int dtype,
@@ -167,6 +175,9 @@ int stpy_trsm_right_lt(int dtype, int64_t m, int64_t n, const void* L, int64_t l
  *   (u = scaled coordinate difference) for the kernel family `kind` (SE, MATERN12/32/52).
  *   work: stpy_gram_workspace_bytes(dtype, n, n, d).  The per-coordinate sums sum_ij H_ij u_m^2 then
  *   follow from H [Xs | 1] (one stpy_gemm_nt) -- see stpy_amd/continuous_processes/gauss_procc.py.
+ *   F comes from the norm expansion of stpy_gram's workspace route (points relative to x_0, same accuracy of r^2).  MATERN12's
+ *   F = exp(-r) / r has no value at r = 0: where r^2 is below the rounding noise of the expansion, 16 eps (|x_i'|^2 + |x_j'|^2), the
+ *   pair counts as coincident and F_ij = 0 -- what F multiplies, u_m^2 <= r^2, vanishes to the same accuracy.
  */
 int stpy_potri(int dtype, int64_t n, const void* L, int64_t ldl, const void* winv, int64_t winv_elems,
                void* Kinv, int64_t ldk, void* work, int64_t work_bytes, void* stream);
@@ -260,17 +271,26 @@ int stpy_tril(int dtype, int64_t n, void* A, int64_t lda, void* stream);
  * (gauss_procc.py:179-184), tr(V^-1) of KernelizedFeatures.effective_dim (kernelized_features.py:103-106) */
 int stpy_trace_dot(int dtype, int64_t n, const void* A, int64_t lda, const void* u, const void* v, void* out2, void* stream);
 
-/* out[k*ldo + i] = x[i*ldx + cols[k]] * inv_ls[k] for k < d (cols NULL: k), and out[d*ldo + i] = 1 when ones_row != 0:
- * [Xs | 1]^T, the "row x K" operand of the evidence gradient's H [Xs | 1] product (see stpy_lml_weight). out: (d + ones_row) x n. */
+/* out[k*ldo + i] = x[i*ldx + cols[k]] * inv_ls[k] for k < d (cols NULL: k), and out[d*ldo + i] = 1 when ones_row & 1:
+ * [Xs | 1]^T, the "row x K" operand of the evidence gradient's H [Xs | 1] product (see stpy_lml_weight). out: (d + (ones_row & 1)) x n.
+ * ones_row & 2: the coordinates are taken relative to the first row of x, out[k*ldo + i] = (x[i*ldx + cols[k]] - x[cols[k]]) * inv_ls[k]
+ * (subtracted before the scaling): the operand of stpy_lml_grad_reduce_centred (ones_row = 3). */
 int stpy_scaled_points_t(int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
                          void* out, int64_t ldo, int ones_row, void* stream);
 
 /* The last step of the evidence gradient w.r.t. the lengthscales of one kernel term: with P = H [Xs | 1] (n x (d+1), ldp >= d+1),
  *   acc[pidx[k]] += inv_ls[k] * sum_i ( xs_ik^2 P_id - xs_ik P_ik ),   xs_ik = x[i*ldx + cols[k]] * inv_ls[k],   k < d
- * ( = inv_ls[k]/2 * sum_ij H_ij (xs_ik - xs_jk)^2 ).  pidx: device int32[d], the parameter slot of coordinate k (all zero for an
- * isotropic 'gamma'; NULL: k); acc is accumulated in coordinate order by one workgroup, so the result is reproducible. */
+ * ( = inv_ls[k]/2 * sum_ij H_ij (xs_ik - xs_jk)^2 for the symmetric H of stpy_lml_weight, which is what is evaluated: the sum is formed
+ * about the first point, sum_i t_ik^2 P_id - t_ik (P_ik - xs_0k P_id) with t = xs - xs_0, so that its own terms are of the size of the
+ * data's extent and not of its distance from the origin ).  pidx: device int32[d], the parameter slot of coordinate k (all zero for an
+ * isotropic 'gamma'; NULL: k); acc is accumulated in coordinate order by one workgroup, so the result is reproducible.
+ * stpy_lml_grad_reduce_centred: the same sum from P = H [T | 1], T the coordinates relative to the first point (T^T from
+ * stpy_scaled_points_t with ones_row = 3): sum_i t_ik^2 P_id - t_ik P_ik.  P = H Xs carries rounding of the size eps |xs| |H|, which the
+ * form above cannot remove; this one is as accurate at any offset of the data as on centred data (what GaussianProcess uses). */
 int stpy_lml_grad_reduce(int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
                          const void* P, int64_t ldp, const int32_t* pidx, void* acc, void* stream);
+int stpy_lml_grad_reduce_centred(int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+                                 const void* P, int64_t ldp, const int32_t* pidx, void* acc, void* stream);
 
 /* The same for a full-covariance item (kernels.py:464-549: z = x[:, cols] cov (n x p), then SE / Matern of |z_i - z_j|; the reference differentiates
  * it by autograd).  With H formed by stpy_lml_weight on the mapped points z (unit lengthscales) and P = H [Z | 1] (n x (p+1)):

@@ -59,6 +59,7 @@ SIGNATURES = {
 	"stpy_trace_dot": (_i32, [_i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
 	"stpy_scaled_points_t": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp]),
 	"stpy_lml_grad_reduce": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+	"stpy_lml_grad_reduce_centred": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 	"stpy_lml_grad_cov_reduce": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
 	"stpy_gram_grad_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i32]),
 	"stpy_gram_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
@@ -359,11 +360,12 @@ def symmetrize_lower(A):
 	_launch("stpy_symmetrize_lower", dtype_code(A.dtype), A.shape[0], ptr(A), ld(A))
 
 
-def scaled_points_t(x, inv_ls, cols=None):
-	"""[Xs | 1]^T, (d + 1, n): the rows of x[:, cols] * inv_ls as columns, then a row of ones."""
+def scaled_points_t(x, inv_ls, cols=None, centre=False):
+	"""[Xs | 1]^T, (d + 1, n): the rows of x[:, cols] * inv_ls as columns, then a row of ones.  centre: coordinates relative to x[0] (the
+	operand lml_grad_reduce(centred=True) expects)."""
 	n, d = x.shape[0], _ncols(x, cols)
 	out = torch.empty((d + 1, n), dtype=x.dtype, device=x.device)
-	_launch("stpy_scaled_points_t", dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), ptr(out), ld(out), 1)
+	_launch("stpy_scaled_points_t", dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), ptr(out), ld(out), 3 if centre else 1)
 	return out
 
 
@@ -375,9 +377,10 @@ def lml_weight(kind, x, inv_ls, kappa, weight, alpha, Kinv, H, cols=None):
 			ptr(H), ld(H), ptr(work), work.numel())
 
 
-def lml_grad_reduce(x, inv_ls, P, pidx, acc, cols=None):
-	_launch("stpy_lml_grad_reduce", dtype_code(x.dtype), ptr(x), x.shape[0], ld(x), _ncols(x, cols), ptr(cols), ptr(inv_ls), ptr(P), ld(P), ptr(pidx),
-			ptr(acc))
+def lml_grad_reduce(x, inv_ls, P, pidx, acc, cols=None, centred=False):
+	"""acc[pidx[k]] += inv_ls[k] / 2 sum_ij H_ij (xs_ik - xs_jk)^2 from P = H [Xs | 1]; centred: P = H [Xs - xs_0 | 1] (scaled_points_t(centre=True))."""
+	_launch("stpy_lml_grad_reduce_centred" if centred else "stpy_lml_grad_reduce", dtype_code(x.dtype), ptr(x), x.shape[0], ld(x), _ncols(x, cols), ptr(cols),
+			ptr(inv_ls), ptr(P), ld(P), ptr(pidx), ptr(acc))
 
 
 def lml_grad_cov_reduce(x, z, P, out, cols=None):

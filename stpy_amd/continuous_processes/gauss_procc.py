@@ -339,15 +339,19 @@ class GaussianProcess(Estimator):
 			nwinv[:_lib.potrf_winv_elems(n0p)].copy_(winv[:_lib.potrf_winv_elems(n0p)])
 			buf, winv = nbuf, nwinv
 			self._L = None
-		# the new rows of K + s^2 I straight into the factor's buffer: K(x_new, x_old) and the lower part of K(x_new, x_new)
-		self.kernel_object._kernel_into(self._xd, xd_new, buf[n0:n1, :n0])
-		self.kernel_object._kernel_into(xd_new, xd_new, buf[n0:n1, n0:n1], diag_add=float(self.s) ** 2, lower_only=True)
+		# the new rows of K + s^2 I straight into the factor's buffer, as ONE launch against all the points: the norm-expansion routes
+		# of stpy_gram expand about the first row of `a`, and with a = [x_old; x_new] that is x_0 -- the point a fit on all the data
+		# expands about -- so every entry comes out bit for bit as a refit would compute it (two launches, one of them with a = x_new,
+		# gave the new diagonal block other roundings, which an ill-conditioned fp32 factor amplifies)
+		xd_all = torch.cat((self._xd, xd_new), dim=0)
+		self.kernel_object._kernel_into(xd_all, xd_new, buf[n0:n1, :n1])
+		_lib.combine(buf[n0:n1, n0:n1], buf[n0:n1, n0:n1], _lib.OUT_SET, float(self.s) ** 2)
 		z = torch.zeros((n1p,), dtype=dtype, device=dev)
 		z[:n0] = self._z[:n0]
 		# from here on the object describes the new data set, fitted only once the extended factor is known to be good (the rows just
 		# written into the buffer overwrote the identity padding of the old factor)
 		self.x, self.y, self.n = x, y, n1
-		self._xd = torch.cat((self._xd, xd_new), dim=0)
+		self._xd = xd_all
 		self._yd = torch.cat((self._yd, yd_new.reshape(-1, 1)), dim=0)
 		self.fitted = False
 		self._alpha_cache = self._Lr = self._winvr = None
@@ -823,9 +827,11 @@ class GaussianProcess(Estimator):
 						tmp = torch.empty((n, n), dtype=L.dtype, device=L.device)
 					kernel._run_items(fac, xd, xd, tmp)
 					_lib.combine(H, tmp, _lib.OUT_MUL)
-				# [Xs | 1]^T (dg + 1, n): scaled coordinates as the NT operand, then P = H [Xs | 1] and the per-coordinate sums
+				# [Xs | 1]^T (dg + 1, n): scaled coordinates as the NT operand, then P = H [Xs | 1] and the per-coordinate sums (for the
+				# lengthscale sums the coordinates are taken relative to the first point: the sums do not see the translation, their
+				# rounding does; the full-covariance reduction works on the points as they are)
 				dg = kd
-				XT = _lib.scaled_points_t(kx, inv_ls, kcols)
+				XT = _lib.scaled_points_t(kx, inv_ls, kcols, centre=premap is None)
 				P = torch.empty((n, dg + 1), dtype=xd.dtype, device=xd.device)
 				_lib.gemm_nt(H, XT, P)
 				a_ = acc[(str(i), term['pname'])]
@@ -835,7 +841,7 @@ class GaussianProcess(Estimator):
 					_lib.lml_grad_cov_reduce(xd, kx, P, a_, cols)
 					continue
 				pidx = _dev_const([int(v) for v in term['pidx']], None, xd.device, int32=True)
-				_lib.lml_grad_reduce(xd, inv_ls, P, pidx, a_, cols)
+				_lib.lml_grad_reduce(xd, inv_ls, P, pidx, a_, cols, centred=True)
 		del work, work_p
 		for key, name, t in wanted:
 			if (key, name) not in acc or int(key) >= len(items) or not any(tm['pname'] == name for tm in items[int(key)]['terms']):

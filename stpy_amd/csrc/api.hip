@@ -412,16 +412,28 @@ int stpy_scaled_points_t(int dtype, const void* x, int64_t n, int64_t ldx, int d
 	         scaled_points_t<float>((const float*)x, n, ldx, d, cols, (const float*)inv_ls, (float*)out, ldo, ones_row, st));
 }
 
+static int lml_grad_reduce_api(const char* who, int centred, int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+                               const void* P, int64_t ldp, const int32_t* pidx, void* acc, void* stream)
+{
+	if (n <= 0 || d <= 0) return 0;
+	if (!x || !inv_ls || !P || !acc) { set_error("%s: null pointer", who); return -2; }
+	if (ldx < 1 || (!cols && ldx < d) || ldp < d + 1) { set_error("%s: bad dimensions", who); return -9; }
+	hipStream_t st = (hipStream_t)stream;
+	DISPATCH(dtype,
+	         lml_grad_reduce<double>((const double*)x, n, ldx, d, cols, (const double*)inv_ls, (const double*)P, ldp, pidx, (double*)acc, centred, st),
+	         lml_grad_reduce<float>((const float*)x, n, ldx, d, cols, (const float*)inv_ls, (const float*)P, ldp, pidx, (float*)acc, centred, st));
+}
+
 int stpy_lml_grad_reduce(int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
                          const void* P, int64_t ldp, const int32_t* pidx, void* acc, void* stream)
 {
-	if (n <= 0 || d <= 0) return 0;
-	if (!x || !inv_ls || !P || !acc) { set_error("stpy_lml_grad_reduce: null pointer"); return -2; }
-	if (ldx < 1 || (!cols && ldx < d) || ldp < d + 1) { set_error("stpy_lml_grad_reduce: bad dimensions"); return -9; }
-	hipStream_t st = (hipStream_t)stream;
-	DISPATCH(dtype,
-	         lml_grad_reduce<double>((const double*)x, n, ldx, d, cols, (const double*)inv_ls, (const double*)P, ldp, pidx, (double*)acc, st),
-	         lml_grad_reduce<float>((const float*)x, n, ldx, d, cols, (const float*)inv_ls, (const float*)P, ldp, pidx, (float*)acc, st));
+	return lml_grad_reduce_api("stpy_lml_grad_reduce", 0, dtype, x, n, ldx, d, cols, inv_ls, P, ldp, pidx, acc, stream);
+}
+
+int stpy_lml_grad_reduce_centred(int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+                                 const void* P, int64_t ldp, const int32_t* pidx, void* acc, void* stream)
+{
+	return lml_grad_reduce_api("stpy_lml_grad_reduce_centred", 1, dtype, x, n, ldx, d, cols, inv_ls, P, ldp, pidx, acc, stream);
 }
 
 int stpy_lml_grad_cov_reduce(int dtype, const void* x, int64_t n, int64_t ldx, int dg, const int32_t* cols,

@@ -183,7 +183,7 @@ int lml_grad_cov_reduce(const T* x, int64_t n, int64_t ldx, int dg, const int32_
                         T* out, hipStream_t st);
 template <typename T>
 int lml_grad_reduce(const T* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const T* inv_ls, const T* P, int64_t ldp,
-                    const int32_t* pidx, T* acc, hipStream_t st);
+                    const int32_t* pidx, T* acc, int centred, hipStream_t st);
 template <typename T>
 int gram(int kind, const T* a, int64_t n, int64_t lda, const T* b, int64_t q, int64_t ldb, int d,
          const int32_t* cols, const T* inv_ls, double kappa, double offset, double diag_add,

@@ -179,7 +179,10 @@ template <typename T, int KIND> __device__ __forceinline__ T gram_dfactor(T acc,
 	const T sq = na + nb - T(2) * acc;
 	if (KIND == STPY_K_SE) return gram_exp(T(-0.5) * sq);
 	const T rr = sqrt(fmax(sq, T(0)));
-	if (KIND == STPY_K_MATERN12) return rr > T(0) ? gram_exp(-rr) / rr : T(0);
+	// exp(-r) / r: r^2 from the expansion carries rounding noise of a few eps (|a|^2 + |b|^2), so on coincident points it is 0 or ~1e-16
+	// by the last bit and 1 / r anything up to 1e8.  Below that noise floor the pair is coincident as far as this route can tell, and
+	// the factor is 0 -- what it multiplies, u_m^2 <= r^2, is zero to the same accuracy.
+	if (KIND == STPY_K_MATERN12) return sq > T(16) * (sizeof(T) == 8 ? T(2.220446049250313e-16) : T(1.1920929e-7)) * (na + nb) ? gram_exp(-rr) / rr : T(0);
 	if (KIND == STPY_K_MATERN32) return T(3) * gram_exp(-rr * T(1.7320508075688772935));
 	const T r = rr * T(2.2360679774997896964);                       // MATERN52
 	return T(1.6666666666666666667) * (T(1) + r) * gram_exp(-r);

@@ -9,7 +9,12 @@
 // wave-wide broadcasts), row/column squared norms accumulated while staging.
 //
 // Distance forms (they follow the reference per kernel family):
-//   SE / ARD      : ||a||^2 + ||b||^2 - 2<a,b>  (norm expansion, kernels.py:390-398, no clamp)
+//   SE / ARD      : ||a||^2 + ||b||^2 - 2<a,b>  (norm expansion, kernels.py:390-398, no clamp) of the points taken RELATIVE TO THE
+//                    FIRST ROW OF a: a stationary kernel does not see a common translation, and the rounding error of the expansion
+//                    grows with the squared distance of the points from the origin of the expansion -- about a point of the data it
+//                    is proportional to the squared diameter of the scaled data, wherever the data lies ("Gram accuracy
+//                    off the unit cube").  The reference row is read from device memory by every thread that stages a point and
+//                    subtracted BEFORE the multiplication by the inverse lengthscale; a and b of one call share it.
 //   Matern 1/2..5/2: sum_k (a_k - b_k)^2        (direct differences as scipy/torch cdist,
 //                    kernels.py:843, :944 -- exact zero on coincident points, which nu = 1/2 needs)
 #include "common.h"
@@ -25,6 +30,7 @@ struct GramArgs {
 	int n, q, d;
 	T kappa, offset, diag_add;
 	int kind, lower_only, combine, degree;
+	int centre;          // stationary kinds on the norm expansion: coordinates relative to a's first row
 };
 
 template <typename T> __device__ __forceinline__ T int_power(T base, int degree)
@@ -77,7 +83,10 @@ void gram_kernel(GramArgs<T> p)
 				const int k = kh * (GT_K / 2) + kk;
 				const int kg = k0 + k;
 				T v = T(0);
-				if (kg < p.d) v = p.a[(int64_t)gi * p.lda + (p.cols ? p.cols[kg] : kg)] * p.inv_ls[kg];
+				if (kg < p.d) {
+					const int c = p.cols ? p.cols[kg] : kg;
+					v = (p.a[(int64_t)gi * p.lda + c] - (p.centre ? p.a[c] : T(0))) * p.inv_ls[kg];
+				}
 				as[k][pt] = v;
 			}
 		}
@@ -89,7 +98,10 @@ void gram_kernel(GramArgs<T> p)
 				const int k = kq * (GT_K / 4) + kk;
 				const int kg = k0 + k;
 				T v = T(0);
-				if (kg < p.d) v = p.b[(int64_t)gj * p.ldb + (p.cols ? p.cols[kg] : kg)] * p.inv_ls[kg];
+				if (kg < p.d) {
+					const int c = p.cols ? p.cols[kg] : kg;
+					v = (p.b[(int64_t)gj * p.ldb + c] - (p.centre ? p.a[c] : T(0))) * p.inv_ls[kg];
+				}
 				bs[pt][k] = v;
 			}
 		}
@@ -159,21 +171,25 @@ void gram_kernel(GramArgs<T> p)
 // epilogue: the fp64 vector ALU -- the bottleneck of the tile kernel above, which needs ~60
 // instructions per element -- is left with the ~25 of the exp.  The points are first gathered
 // (column subset), scaled by the inverse lengthscales and zero-padded to a whole K tile (16 doubles / 32 floats)
-// of coordinates into the caller's workspace, together with their squared norms.
+// of coordinates into the caller's workspace, together with their squared norms.  For the stationary kinds the coordinates are taken
+// relative to `ref` (the first row of the call's `a`, for both operands) before they are scaled: see the note on distance forms above.
 // Matern 1/2 keeps the direct-difference tile kernel: exp(-r) has a first-order term in r, and
 // r from the norm expansion is only good to ~1e-8 on coincident points.
 // ------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256)
 void prep_points_kernel(const T* __restrict__ x, int64_t n, int64_t ldx, int d, int dpad, const int32_t* cols, const T* __restrict__ inv_ls,
-                        T* __restrict__ xs, T* __restrict__ nx)
+                        const T* __restrict__ ref, T* __restrict__ xs, T* __restrict__ nx)
 {
 	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
 	if (i >= n) return;
 	T s = T(0);
 	for (int k = 0; k < dpad; ++k) {
 		T v = T(0);
-		if (k < d) v = x[i * ldx + (cols ? cols[k] : k)] * inv_ls[k];
+		if (k < d) {
+			const int c = cols ? cols[k] : k;
+			v = (x[i * ldx + c] - (ref ? ref[c] : T(0))) * inv_ls[k];
+		}
 		xs[i * dpad + k] = v;
 		s += v * v;
 	}
@@ -208,9 +224,10 @@ int gram(int kind, const T* a, int64_t n, int64_t lda, const T* b, int64_t q, in
 		T* na = (T*)w; w += align16(n * sizeof(T));
 		T* nb = (T*)w;
 		const bool same = (a == b) && (n == q) && (lda == ldb);
-		hipLaunchKernelGGL((prep_points_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, n, lda, d, dpad, cols, inv_ls, as, na);
+		const T* ref = kind == STPY_K_LINEAR ? nullptr : a;          // the dot-product kinds are not translation invariant
+		hipLaunchKernelGGL((prep_points_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, n, lda, d, dpad, cols, inv_ls, ref, as, na);
 		if (same) { bs = as; nb = na; }
-		else hipLaunchKernelGGL((prep_points_kernel<T>), dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, b, q, ldb, d, dpad, cols, inv_ls, bs, nb);
+		else hipLaunchKernelGGL((prep_points_kernel<T>), dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st, b, q, ldb, d, dpad, cols, inv_ls, ref, bs, nb);
 		int rc = check_launch("gram prep");
 		if (rc) return rc;
 		if constexpr (sizeof(T) == 8) {          // aligned overwriting fp64 fills: the dedicated kernel (three small workgroups per CU)
@@ -229,6 +246,7 @@ int gram(int kind, const T* a, int64_t n, int64_t lda, const T* b, int64_t q, in
 	p.n = (int)n; p.q = (int)q; p.d = d;
 	p.kappa = (T)kappa; p.offset = (T)offset; p.diag_add = (T)diag_add;
 	p.kind = kind; p.lower_only = lower_only; p.combine = combine; p.degree = degree;
+	p.centre = kind == STPY_K_SE;          // (the Matern kinds take direct differences here, LINEAR / POLY are not translation invariant)
 	dim3 grid((unsigned)((n + GT_I - 1) / GT_I), (unsigned)((q + GT_J - 1) / GT_J));
 	if (grid.y > 65535u) { set_error("gram: q too large for one launch"); return -7; }
 	const bool direct = (kind == STPY_K_MATERN12 || kind == STPY_K_MATERN32 || kind == STPY_K_MATERN52);
@@ -301,7 +319,7 @@ int lml_weight(int kind, const T* x, int64_t n, int64_t ldx, int d, const int32_
 	T* as = (T*)w; w += align16(n * (int64_t)dpad * sizeof(T));
 	w += align16(n * (int64_t)dpad * sizeof(T));
 	T* na = (T*)w;
-	hipLaunchKernelGGL((prep_points_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, ldx, d, dpad, cols, inv_ls, as, na);
+	hipLaunchKernelGGL((prep_points_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, ldx, d, dpad, cols, inv_ls, x, as, na);
 	int rc = check_launch("lml_weight prep");
 	if (rc) return rc;
 	GramEpilogue<T> epi{kind, 0, (T)kappa, T(0), T(0), na, na, alpha, (T)weight};

@@ -74,17 +74,18 @@ int trace_dot(int64_t n, const T* A, int64_t lda, const T* u, const T* v, T* out
 	return check_launch("trace_dot");
 }
 
-// out[k*ldo + i] = x[i*ldx + cols[k]] * inv_ls[k]  (k < d),  and out[d*ldo + i] = 1 when ones_row: the NT operand [Xs | 1]^T
+// out[k*ldo + i] = (x[i*ldx + cols[k]] - [centre] x[cols[k]]) * inv_ls[k]  (k < d),  and out[d*ldo + i] = 1 when ones: the NT operand
+// [Xs | 1]^T, with `centre` of the coordinates relative to the first point (subtracted before the scaling)
 template <typename T>
 __global__ __launch_bounds__(256)
 void scaled_points_t_kernel(const T* __restrict__ x, int64_t ldx, int n, int d, const int32_t* __restrict__ cols, const T* __restrict__ inv_ls,
-                            T* __restrict__ out, int64_t ldo)
+                            T* __restrict__ out, int64_t ldo, int centre)
 {
 	const int i = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
 	if (i >= n) return;
 	if (k == d) { out[(int64_t)k * ldo + i] = T(1); return; }
 	const int c = cols ? cols[k] : k;
-	out[(int64_t)k * ldo + i] = x[(int64_t)i * ldx + c] * inv_ls[k];
+	out[(int64_t)k * ldo + i] = (x[(int64_t)i * ldx + c] - (centre ? x[c] : T(0))) * inv_ls[k];
 }
 
 template <typename T>
@@ -92,29 +93,35 @@ int scaled_points_t(const T* x, int64_t n, int64_t ldx, int d, const int32_t* co
 {
 	if (n <= 0) return 0;
 	if (n > INT32_MAX) { set_error("scaled_points_t: n exceeds int32"); return -2; }
-	hipLaunchKernelGGL((scaled_points_t_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)(d + (ones_row ? 1 : 0))), dim3(256), 0, st,
-	                   x, ldx, (int)n, d, cols, inv_ls, out, ldo);
+	hipLaunchKernelGGL((scaled_points_t_kernel<T>), dim3((unsigned)((n + 255) / 256), (unsigned)(d + (ones_row & 1))), dim3(256), 0, st,
+	                   x, ldx, (int)n, d, cols, inv_ls, out, ldo, (ones_row >> 1) & 1);
 	return check_launch("scaled_points_t");
 }
 
 // With P = H [Xs | 1]  (n x (d+1); column d = h = H 1):
 //   S_k = sum_i xs_ik^2 h_i - xs_ik P_ik  ( = 1/2 sum_ij H_ij (xs_ik - xs_jk)^2 for symmetric H ),
 //   acc[pidx[k]] += S_k * inv_ls[k]                 -- d/d(lengthscale) of the evidence per coordinate of a kernel term
+// The sum does not see a common translation of the points, but formed about the origin its two halves each grow with the square of
+// the data's distance from it and then cancel.  So it is formed about the first point: with xs = c0 + t,
+//   S_k = sum_i t_i^2 h_i - t_i (H t)_i,     (H t)_i = P_ik - c0 h_i     (H symmetric)
+// `centred`: P was formed from t already (stpy_scaled_points_t, ones_row = 3), (H t)_i = P_ik -- P = H Xs carries rounding of the
+// size eps |xs| |H| that no later step removes, so this is the form whose accuracy does not depend on where the data lies.
 // One workgroup, coordinates in order: several coordinates that share a parameter (an isotropic 'gamma') are added in a fixed order.
 template <typename T>
 __global__ __launch_bounds__(1024)
 void lml_grad_reduce_kernel(const T* __restrict__ x, int64_t ldx, int n, int d, const int32_t* __restrict__ cols, const T* __restrict__ inv_ls,
-                            const T* __restrict__ P, int64_t ldp, const int32_t* __restrict__ pidx, T* __restrict__ acc)
+                            const T* __restrict__ P, int64_t ldp, const int32_t* __restrict__ pidx, T* __restrict__ acc, int centred)
 {
 	__shared__ T red[16];
 	for (int k = 0; k < d; ++k) {
 		const int c = cols ? cols[k] : k;
 		const T il = inv_ls[k];
+		const T x0 = x[c], c0 = centred ? T(0) : x0 * il;
 		T s = T(0);
 		for (int i = threadIdx.x; i < n; i += 1024) {
-			const T xs = x[(int64_t)i * ldx + c] * il;
+			const T t = (x[(int64_t)i * ldx + c] - x0) * il;
 			const T* Pi = P + (int64_t)i * ldp;
-			s += xs * xs * Pi[d] - xs * Pi[k];
+			s += t * (t * Pi[d] - fma(-c0, Pi[d], Pi[k]));
 		}
 		s = block_sum_1024(s, red);
 		if (threadIdx.x == 0) acc[pidx ? pidx[k] : k] += s * il;
@@ -123,10 +130,10 @@ void lml_grad_reduce_kernel(const T* __restrict__ x, int64_t ldx, int n, int d, 
 
 template <typename T>
 int lml_grad_reduce(const T* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const T* inv_ls, const T* P, int64_t ldp,
-                    const int32_t* pidx, T* acc, hipStream_t st)
+                    const int32_t* pidx, T* acc, int centred, hipStream_t st)
 {
 	if (n > INT32_MAX) { set_error("lml_grad_reduce: n exceeds int32"); return -2; }
-	hipLaunchKernelGGL((lml_grad_reduce_kernel<T>), dim3(1), dim3(1024), 0, st, x, ldx, (int)n, d, cols, inv_ls, P, ldp, pidx, acc);
+	hipLaunchKernelGGL((lml_grad_reduce_kernel<T>), dim3(1), dim3(1024), 0, st, x, ldx, (int)n, d, cols, inv_ls, P, ldp, pidx, acc, centred);
 	return check_launch("lml_grad_reduce");
 }
 
@@ -168,7 +175,7 @@ int lml_grad_cov_reduce(const T* x, int64_t n, int64_t ldx, int dg, const int32_
 	template int tril<T>(int64_t, T*, int64_t, hipStream_t); \
 	template int trace_dot<T>(int64_t, const T*, int64_t, const T*, const T*, T*, hipStream_t); \
 	template int scaled_points_t<T>(const T*, int64_t, int64_t, int, const int32_t*, const T*, T*, int64_t, int, hipStream_t); \
-	template int lml_grad_reduce<T>(const T*, int64_t, int64_t, int, const int32_t*, const T*, const T*, int64_t, const int32_t*, T*, hipStream_t);
+	template int lml_grad_reduce<T>(const T*, int64_t, int64_t, int, const int32_t*, const T*, const T*, int64_t, const int32_t*, T*, int, hipStream_t);
 INST(double)
 INST(float)
 

@@ -1263,3 +1263,114 @@ def test_bench_plain_run_times_steps_and_dumps_outputs(S, tmp_path):
 	L, alpha = O.fit(x.numpy(), y.numpy(), spec, 0.1)
 	mu_o, std_o = O.mean_std(x.numpy(), L, alpha, xt.numpy(), spec)
 	assert rel_err(mu.reshape(-1), mu_o.reshape(-1)) < 1e-8 and rel_err(std.reshape(-1), std_o.reshape(-1)) < 1e-8
+
+
+# ------------------------------------------------------------------------------------------ translated inputs
+# A stationary kernel does not see a common translation of the inputs: (x + c, y) predicted at xt + c is the problem (x, y, xt).
+# Inputs sit on the dyadic grid of tests/gram_edge_cases.py and c is an integer (1000 in fp64, 100 in fp32), so x + c is stored
+# exactly and the two problems have exactly the same pairwise differences.  The oracle on the CENTRED points is the high-precision
+# side (its own SE on the shifted points carries the cancellation of the norm expansion); tolerances are the ones this file uses on
+# centred data: TOL for fp64 predictions, 1e-9 / 1e-7 for the evidence and its gradient (test_log_marginal_gradient_isotropic),
+# 1e-3 for fp32 (test_fp32_mode).
+from tests import gram_edge_cases as E          # noqa: E402
+from tests.test_posterior_grad import make_kernel, posterior_grads          # noqa: E402
+
+_TR_D = 3
+# name -> (kernel items for make_kernel, oracle spec, overrides handed to log_marginal as {item: (param, value, extra keys)})
+_TR_CASES = {
+	"se": ([("-", dict(kernel_name="squared_exponential", gamma=2.0, kappa=1.3))],
+	       [("squared_exponential", {"gamma": 2.0, "kappa": 1.3}, "-")], {"0": ("gamma", [2.0], {})}),
+	"ard": ([("-", dict(kernel_name="ard", ard_gamma=[1.0, 2.0, 4.0], kappa=1.1))],
+	        [("ard", {"ard_gamma": np.array([1.0, 2.0, 4.0]), "kappa": 1.1}, "-")], {"0": ("ard_gamma", [1.0, 2.0, 4.0], {})}),
+	"m12": ([("-", dict(kernel_name="matern", gamma=2.0, nu=0.5, kappa=1.3))],
+	        [("matern", {"gamma": 2.0, "nu": 0.5, "kappa": 1.3}, "-")], {"0": ("gamma", [2.0], {"nu": 0.5})}),
+	"m32": ([("-", dict(kernel_name="matern", gamma=2.0, nu=1.5, kappa=1.3))],
+	        [("matern", {"gamma": 2.0, "nu": 1.5, "kappa": 1.3}, "-")], {"0": ("gamma", [2.0], {"nu": 1.5})}),
+	"m52": ([("-", dict(kernel_name="matern", gamma=2.0, nu=2.5, kappa=1.3))],
+	        [("matern", {"gamma": 2.0, "nu": 2.5, "kappa": 1.3}, "-")], {"0": ("gamma", [2.0], {"nu": 2.5})}),
+	"se_times_se": ([("-", dict(kernel_name="squared_exponential", gamma=2.0, kappa=1.2)),
+	                 ("*", dict(kernel_name="squared_exponential", gamma=4.0, kappa=0.8, group=[1, 2]))],
+	                [("squared_exponential", {"gamma": 2.0, "kappa": 1.2}, "-"), ("squared_exponential", {"gamma": 4.0, "kappa": 0.8, "group": [1, 2]}, "*")],
+	                {"0": ("gamma", [2.0], {}), "1": ("gamma", [4.0], {})}),
+}
+
+
+def _tr_data(dt, n=200, m=40, coincident=False):
+	rng = np.random.RandomState(41)
+	grid = E.GRID[dt]
+	x = rng.randint(-grid, grid + 1, size=(n, _TR_D)) / float(grid)
+	xt = rng.randint(-grid, grid + 1, size=(m, _TR_D)) / float(grid)
+	if coincident:
+		x[1] = x[0]
+	y = 1.5 * np.sin(3 * x[:, :1]) + 0.75 * x[:, 1:2] + 0.15 * rng.normal(size=(n, 1))
+	if dt == "f32":
+		y = y.astype(np.float32).astype(np.float64)
+	return x, y, xt
+
+
+def _tr_oracle_lml_grad(x, y, ospec, s):
+	"""Value and lengthscale gradients of the evidence from the oracle's analytic forms.  Its Matern derivative lives in the
+	full-covariance item (z = x cov, d/dcov): an isotropic Matern of lengthscale g is that item at cov = I / g, and
+	d/dg = -1/g^2 sum_a d/dcov[a][a]."""
+	conv, back = [], {}
+	for i, (name, p, op) in enumerate(ospec):
+		if name == "matern":
+			d = x.shape[1]
+			conv.append(("full_covariance_matern", {"cov": np.eye(d) / p["gamma"], "nu": p["nu"], "kappa": p["kappa"]}, op))
+			back[i] = p["gamma"]
+		else:
+			conv.append((name, p, op))
+	val, grads, _ = O.log_marginal_grad(x, y, conv, s)
+	out = {}
+	for i, g in grads.items():
+		if i in back:
+			d = x.shape[1]
+			out[str(i)] = np.array([-np.sum(g["cov"].reshape(d, d).diagonal()) / back[i] ** 2])
+		else:
+			out[str(i)] = np.asarray(list(g.values())[0])
+	return float(val[0, 0]), out
+
+
+def _tr_check(S, case, dt, coincident=False):
+	items, ospec, overrides = _TR_CASES[case]
+	x, y, xt = _tr_data(dt, coincident=coincident)
+	c = float(E.OFFSET[dt])
+	tdt = torch.float64 if dt == "f64" else torch.float32
+	s = 0.2 if dt == "f64" else 0.3
+	tol_pred, tol_val, tol_grad = (TOL, 1e-9, 1e-7) if dt == "f64" else (1e-3, 1e-3, 1e-3)
+	xs, xts = x + c, xt + c
+	assert np.array_equal(xs.astype(np.float32 if dt == "f32" else np.float64).astype(np.float64) - c, x)          # the shift is exact
+	kernel = make_kernel(items, d=_TR_D)
+	GP = S.GaussianProcess(kernel=kernel, s=s, d=_TR_D)
+	GP.fit_gp(torch.from_numpy(xs).to(tdt), torch.from_numpy(y).to(tdt))
+	mu, std = GP.mean_std(torch.from_numpy(xts).to(tdt))
+	L, alpha = O.fit(x, y, ospec, s)
+	mu_o, std_o = O.mean_std(x, L, alpha, xt, ospec)
+	assert rel_err(N(mu).astype(np.float64), mu_o) < tol_pred, (case, dt, rel_err(N(mu).astype(np.float64), mu_o))
+	assert rel_err(N(std).astype(np.float64), std_o) < tol_pred, (case, dt, rel_err(N(std).astype(np.float64), std_o))
+	# evidence and its lengthscale gradient
+	leaves = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, (_, v, _) in overrides.items()}
+	X = {k: dict({overrides[k][0]: leaves[k]}, **overrides[k][2]) for k in overrides}
+	f = GP.log_marginal(GP.kernel_object, X, 1.0)
+	f.backward()
+	val_o, grad_o = _tr_oracle_lml_grad(x, y, ospec, s)
+	assert abs(float(f.detach()) - val_o) / abs(val_o) < tol_val, (case, dt, float(f.detach()), val_o)
+	for k in overrides:
+		assert rel_err(leaves[k].grad.numpy(), grad_o[k]) < tol_grad, (case, dt, k, leaves[k].grad.numpy(), grad_o[k])
+	# input gradients of the posterior (Matern 1/2 and 3/2 have no derivative at a training point; the test points are none)
+	dmu, dstd = GP.mean_std_grad(torch.from_numpy(xts).to(tdt))
+	_, _, dmu_o, dstd_o, _ = posterior_grads(kernel, x, y, s, xt)
+	assert rel_err(N(dmu).astype(np.float64), dmu_o) < tol_pred, (case, dt, rel_err(N(dmu).astype(np.float64), dmu_o))
+	assert rel_err(N(dstd).astype(np.float64), dstd_o) < tol_pred, (case, dt, rel_err(N(dstd).astype(np.float64), dstd_o))
+
+
+@pytest.mark.parametrize("dt", ["f64", "f32"])
+@pytest.mark.parametrize("case", sorted(_TR_CASES))
+def test_translated_inputs_match_the_centred_oracle(S, case, dt):
+	_tr_check(S, case, dt)
+
+
+def test_translated_coincident_points_matern12_gradient(S):
+	"""Two training points coincide exactly: the Matern 1/2 derivative factor exp(-r) / r has no value there and what it multiplies is
+	zero, so the pair must drop out of the evidence gradient -- on centred and on translated inputs alike."""
+	_tr_check(S, "m12", "f64", coincident=True)

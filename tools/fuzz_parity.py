@@ -1,6 +1,8 @@
 """Randomised parity sweep through the drop-in classes against the CPU oracle (checker only): random sizes (ragged, tiny, around the
 128 / 512 / 1024 tile and panel edges), dimensions, kernel families and hyper-parameters; fit_gp + mean_std (+ full covariance) +
 log_marginal + add_data_point, in fp64 with the 1e-8 bar of SURVEY.md section 8d scaled by the conditioning of the case.
+One case in five of the translation-invariant families moves x and xt by a common integer offset round(10^U(0,3)) (at most 100 in fp32)
+and is compared with the oracle on the UNSHIFTED points: the Gram kernels must not lose digits to where the data lies.
 usage: python tools/fuzz_parity.py [cases] [seed] [rff cases]        exit code 1 on the first failure (the failing case is printed)"""
 import sys
 import time
@@ -19,6 +21,7 @@ for _kv in filter(None, os.environ.get("STPY_TUNE", "").split(",")):          # 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 rng = np.random.RandomState(seed)
+rng_off = np.random.RandomState(seed + 977)          # the offsets have a stream of their own: every older draw of a seed keeps its meaning
 dev = torch.device("cuda:0")
 SIZES = [1, 2, 3, 5, 17, 63, 64, 65, 127, 128, 129, 200, 255, 256, 257, 383, 511, 512, 513, 640, 700, 1023, 1024, 1025, 1300, 2047, 2048, 2100, 3000]
 
@@ -63,6 +66,8 @@ for case in range(cases):
 		k2 = KernelFunction(kernel_name="matern", gamma=1.5 * gamma, nu=nu, kappa=1.0, d=d)
 		ko = (k1 + k2) if fam == "sum" else (k1 * k2)
 		spec = [("squared_exponential", {"gamma": gamma, "kappa": kappa}, "-"), ("matern", {"gamma": 1.5 * gamma, "nu": nu, "kappa": 1.0}, "+" if fam == "sum" else "*")]
+	u_off, e_off = rng_off.uniform(), rng_off.uniform(0, 3)
+	off = float(round(10.0 ** e_off)) if (u_off < 0.2 and fam not in ("linear", "polynomial")) else 0.0
 	desc = "case %d: n=%d d=%d m=%d %s s=%.3g kappa=%.3g gamma=%.3g nu=%.1f" % (case, n, d, m, fam, s, kappa, gamma, nu)
 	try:
 		Ko = O.gram_train(x, spec, s)
@@ -73,11 +78,20 @@ for case in range(cases):
 		tdt = torch.float32 if f32 else torch.float64
 		if f32:
 			tol = max(1e-3, 1e-6 * cond)
+		if off:
+			# the device sees the shifted points rounded to its dtype; the oracle sees exactly those points moved back
+			off = min(off, 100.0) if f32 else off
+			ndt = np.float32 if f32 else np.float64
+			x_dev, xt_dev = (x + off).astype(ndt).astype(np.float64), (xt + off).astype(ndt).astype(np.float64)
+			x, xt = x_dev - off, xt_dev - off
+			desc += " offset=%g" % off
+		else:
+			x_dev, xt_dev = x, xt
 		L, alpha = O.fit(x, y, spec, s)
 		mu_o, sd_o = O.mean_std(x, L, alpha, xt, spec)
 		lml_o = float(O.log_marginal(x, y, spec, s)[0, 0])
 		gp = GaussianProcess(kernel=ko, s=s, d=d)
-		xd, yd, xtd = (torch.from_numpy(v).to(dev).to(tdt) for v in (x, y, xt))
+		xd, yd, xtd = (torch.from_numpy(v).to(dev).to(tdt) for v in (x_dev, y, xt_dev))
 		gp.fit_gp(xd, yd)
 		mu, sd = gp.mean_std(xtd)
 		lml = float(gp.log_marginal(gp.kernel_object, {}, 1.0).item())
