@@ -56,8 +56,9 @@ class _LogMarginalFn(torch.autograd.Function):
 
 
 class _PosteriorFn(torch.autograd.Function):
-	"""Autograd node of GaussianProcess.mean_std for a test tensor with requires_grad: forward = the HIP prediction, backward =
-	one stpy_gram_grad launch per kernel term with u = g_mu, v = -g_sigma / sigma (and W^T = X L^-1 only when g_sigma is nonzero)."""
+	"""Autograd node of ``mean_std`` for a test tensor with requires_grad, for any owner with ``_posterior(xtest) -> (mu, sigma, state)``
+	(device vectors) and ``_posterior_grad(state, gmu, gstd) -> (M, d)``: forward = the HIP prediction, backward = the owner's input
+	gradient (GaussianProcess: one stpy_gram_grad launch per kernel term; KernelizedFeatures: one stpy_rff_grad launch)."""
 
 	@staticmethod
 	def forward(ctx, gp, xtest):
@@ -99,6 +100,84 @@ def _wants_grad(xtest):
 def _tile_pad(n):
 	"""Order at which an n x n SPD matrix is held on the device: the next multiple of the 128 x 128 GEMM tile."""
 	return -(-int(n) // 128) * 128
+
+
+def _draw_starts(multistart, d, bounds):
+	"""``multistart`` uniform starts in the box ``bounds``, drawn with the reference's np.random calls in its order (randn(d), then d
+	uniforms, per start: gauss_procc.py:935-938, kernelized_features.py:515-518), so a seeded run starts where the reference does."""
+	starts = []
+	for _ in range(multistart):
+		x0 = np.random.randn(d)
+		for i in range(d):
+			x0[i] = np.random.uniform(bounds[i][0], bounds[i][1])
+		starts.append(x0)
+	return starts
+
+
+def _multistart_maximize(evaluate, starts, bounds, dev, dtype, final=None):
+	"""All starts as ONE L-BFGS-B problem over the stacked points (the objective is a sum of independent terms): ``evaluate`` maps
+	device points (S, d) to (values (S,), gradients (S, d)), one batched device evaluation per step.  ``final`` maps the solution to
+	its values alone, for a caller whose values come cheaper without gradients (default: those of ``evaluate``).  Returns (solutions
+	(S, d), values (S,), number of evaluations, the final one included) as NumPy float64."""
+	from scipy.optimize import minimize
+	S, d = len(starts), len(starts[0])
+	count = [0]
+
+	def at(z, f):
+		count[0] += 1
+		return f(torch.from_numpy(np.ascontiguousarray(z.reshape(S, d))).to(device=dev, dtype=dtype))
+
+	def fun(z):
+		val, g = at(z, evaluate)
+		return -float(val.sum().item()), -g.double().cpu().numpy().reshape(-1)
+
+	res = minimize(fun, np.concatenate(starts), method="L-BFGS-B", jac=True, bounds=list(bounds) * S,
+				   options=dict(maxiter=15000, ftol=1e-15, gtol=1e-10))
+	vals = at(res.x, final or (lambda xt: evaluate(xt)[0]))
+	return res.x.reshape(S, d), vals.double().cpu().numpy(), count[0]
+
+
+class ResidentFactor:
+	"""The Cholesky factor of one (data, hyper-parameters) pair on the device, and what is derived from it at most once.  An estimator
+	holds it in ``_factor`` and drops all of it with ``_factor = None``.
+	  L, winv   the factor (GaussianProcess: tile-padded, lower triangle) and the inverse 128 x 128 diagonal blocks of stpy_potrf
+	  n         order of the matrix that was factored (L's order without the padding)
+	  buf       the capacity buffer L is a leading view of after an append (room for more rows), else None
+	  z         L^-1 y; None on a factor nobody solved with
+	  key       GaussianProcess._hyper_key of the hyper-parameters it was built from, None where nothing compares it"""
+
+	def __init__(self, L, winv, n=None, z=None, key=None, buf=None):
+		self.L, self.winv, self.n, self.z, self.key, self.buf = L, winv, L.shape[0] if n is None else n, z, key, buf
+		self._alpha = self._reversed = self._inverse = None
+
+	def solve(self, y):
+		"""z = L^-1 y, kept; returns alpha = L^-T z."""
+		self.z, self._alpha = _lib.trsv(self.L, self.winv, y), None
+		return self.alpha
+
+	@property
+	def alpha(self):
+		"""K^-1 y = L^-T z, (n,)."""
+		if self._alpha is None:
+			self._alpha = _lib.trsv(self.L, self.winv, self.z, trans=1)[:self.n]
+		return self._alpha
+
+	def reversed(self):
+		"""(J L^T J, its inverse diagonal blocks) for B L^-1 (stpy_trsm_ln_factor): another matrix of L's size."""
+		if self._reversed is None:
+			self._reversed = _lib.trsm_ln_factor(self.L, self.winv)
+		return self._reversed
+
+	def inverse(self):
+		"""(L L^T)^-1, full symmetric (stpy_potri): read-only for its users."""
+		if self._inverse is None:
+			self._inverse = _lib.potri(self.L, self.winv)
+		return self._inverse
+
+
+def _of_factor(name):
+	"""Read-only estimator property: that field of the resident factor, None without a factor."""
+	return property(lambda self: None if self._factor is None else getattr(self._factor, name))
 
 
 class GaussianProcess(Estimator):
@@ -145,14 +224,10 @@ class GaussianProcess(Estimator):
 		# device state
 		self._xd = None
 		self._yd = None
-		self._L = None          # N x N, lower triangle = Cholesky factor of k(x,x) + Sigma^T Sigma
-		self._winv = None       # inverse 128 x 128 diagonal blocks of L
-		self._z = None          # L^-1 y
 		self._Sigma = None
-		self._alpha_cache = None
-		self._Lbuf = None       # the buffer _L is a leading view of after add_data_point(iterative=True) (capacity for more rows)
-		self._Lr = None         # reversed factor J L^T J and its inverse diagonal blocks (stpy_trsm_ln_factor): built on the first
-		self._winvr = None      # variance gradient after a fit, dropped on refit
+		self._factor = None     # ResidentFactor of k(x,x) + Sigma^T Sigma; ``fitted`` implies there is one
+
+	_L, _winv, _z, _alpha, _Lbuf = (_of_factor(name) for name in ("L", "winv", "z", "alpha", "buf"))
 
 	# ------------------------------------------------------------------ small API mirrors
 	def description(self):
@@ -217,10 +292,10 @@ class GaussianProcess(Estimator):
 		if bad != 0:
 			raise torch.linalg.LinAlgError(what % bad)
 
-	def _factor(self, xd, kwargs=None, Sigma=None, defer_check=False):
-		"""K_theta = k(x,x) + s^2 I (or + Sigma^T Sigma) -> in-place Cholesky.  Returns (L, winv); with ``defer_check`` also the
-		device status word, unread -- the caller enqueues what follows the factorisation first and then calls ``_check_info``,
-		so the device does not idle through the host round trip."""
+	def _factorize(self, kernel, xd, kwargs=None, Sigma=None):
+		"""K_theta = k(x,x) + s^2 I (or + Sigma^T Sigma) of ``kernel`` -> in-place Cholesky.  Returns (ResidentFactor, the device
+		status word, unread): the caller enqueues what follows the factorisation first and then calls ``_check_info``, so the
+		device does not idle through the host round trip."""
 		n0 = xd.shape[0]
 		n = _tile_pad(n0)
 		# The matrix is held at the next multiple of the 128-tile, bordered by an identity block:
@@ -234,24 +309,13 @@ class GaussianProcess(Estimator):
 			Kp[:n0, n0:].zero_()              # (upper part of the last diagonal tile: the diagonal-block kernel loads whole tiles)
 			Kp[n0:, n0:].diagonal().fill_(1.0)
 		if Sigma is None:
-			self.kernel_object._kernel_into(xd, xd, K, kwargs, diag_add=float(self.s) ** 2, lower_only=True)
+			kernel._kernel_into(xd, xd, K, kwargs, diag_add=float(self.s) ** 2, lower_only=True)
 		else:
 			# general noise matrix (gauss_procc.py:163): K += Sigma^T Sigma through the NT product
-			self.kernel_object._kernel_into(xd, xd, K, kwargs)
+			kernel._kernel_into(xd, xd, K, kwargs)
 			self._add_noise_gram(K, Sigma)
-		K = Kp
-		winv, info = _lib.potrf(K, self.nb)
-		if defer_check:
-			return K, winv, info
-		self._check_info(info)
-		return K, winv
-
-	@property
-	def _alpha(self):
-		"""K^-1 y = L^-T z on the device (filled by fit_gp)."""
-		if self._alpha_cache is None and self.fitted:
-			self._alpha_cache = _lib.trsv(self._L, self._winv, self._z, trans=1)[:self.n]
-		return self._alpha_cache
+		winv, info = _lib.potrf(Kp, self.nb)
+		return ResidentFactor(Kp, winv, n0), info
 
 	@property
 	def A(self):
@@ -272,10 +336,7 @@ class GaussianProcess(Estimator):
 		if iterative and xn.shape[0] > 0 and self._can_append(x, Sigma):
 			if self._append(x, y, xn, yn):
 				return None
-		try:
-			self.n, self.d = list(x.size())
-		except Exception:
-			self.n, self.d = x.shape
+		self.n, self.d = x.shape
 		self.x = x
 		self.y = y
 		self._Sigma = Sigma
@@ -284,29 +345,27 @@ class GaussianProcess(Estimator):
 		# not fitted until the new factor exists: a refit that fails (not positive definite, out of memory) leaves an
 		# object that takes the prior branch instead of one that reports fitted=True with no factor behind it
 		self.fitted = False
-		self._L = self._winv = self._z = self._alpha_cache = None       # release the previous factor before allocating the next
-		self._Lr = self._winvr = self._Lbuf = None
-		L, winv, info = self._factor(self._xd, None, Sigma, defer_check=True)
-		z = _lib.trsv(L, winv, self._yd)
+		self._factor = None                                             # release the previous factor before allocating the next
+		F, info = self._factorize(self.kernel_object, self._xd, None, Sigma)
 		# A = K^-1 y is part of the fitted state the reference leaves behind (gauss_procc.py:376): computed
 		# eagerly even though mean_std itself only needs z
-		alpha = _lib.trsv(L, winv, z, trans=1)[:self.n]
+		F.solve(self._yd)
 		# the two vector solves are already queued behind the factorisation when the host reads its status (on a matrix that is
 		# not positive definite they ran on garbage and are dropped with the exception: the object stays unfitted)
 		self._check_info(info)
 		# ... and the sticky device word of the one-launch vector solves: a hand-off wait that gave up has poisoned z / alpha
 		# with NaN (stpy_async_status; the stream is already drained by the read above, so this costs one 4-byte copy)
 		_lib.check_async("fit_gp: stpy_trsv")
-		self._L, self._winv, self._z, self._alpha_cache = L, winv, z, alpha
-		self._factor_key = self._hyper_key(self.kernel_object)
+		F.key = self._hyper_key(self.kernel_object)
+		self._factor = F
 		self.fitted = True
 		return None
 
 	def _can_append(self, x, Sigma):
 		"""The bordered update computes what a refit would: the factor exists and was built from the current s / kernel parameters
 		with the s^2 I noise, and the new points come in its dtype."""
-		return (self.fitted and self._L is not None and Sigma is None and self._Sigma is None
-				and getattr(self, "_factor_key", None) == self._hyper_key(self.kernel_object)
+		return (self.fitted and self._factor is not None and Sigma is None and self._Sigma is None
+				and self._factor.key == self._hyper_key(self.kernel_object)
 				and (x.dtype if torch.is_tensor(x) and x.dtype in (torch.float32, torch.float64) else torch.float64) == self._xd.dtype
 				and x.shape[1] == self._xd.shape[1])
 
@@ -321,9 +380,8 @@ class GaussianProcess(Estimator):
 		n0, k = self.n, xd_new.shape[0]
 		n1 = n0 + k
 		n1p = _tile_pad(n1)
-		buf = getattr(self, "_Lbuf", None)
-		buf = self._L if buf is None else buf
-		winv = self._winv
+		buf = self._L if self._Lbuf is None else self._Lbuf
+		winv, key = self._winv, self._factor.key
 		if n1p > buf.shape[0]:
 			n0p = self._L.shape[0]
 			cap = n1p + 128
@@ -333,12 +391,11 @@ class GaussianProcess(Estimator):
 			except RuntimeError:
 				nbuf = nwinv = None
 				self.fitted = False
-				self._L = self._Lbuf = self._winv = self._z = self._alpha_cache = self._Lr = self._winvr = None
+				self._factor = None
 				return False
 			nbuf[:n0p, :n0p].copy_(self._L)
 			nwinv[:_lib.potrf_winv_elems(n0p)].copy_(winv[:_lib.potrf_winv_elems(n0p)])
 			buf, winv = nbuf, nwinv
-			self._L = None
 		# the new rows of K + s^2 I straight into the factor's buffer, as ONE launch against all the points: the norm-expansion routes
 		# of stpy_gram expand about the first row of `a`, and with a = [x_old; x_new] that is x_0 -- the point a fit on all the data
 		# expands about -- so every entry comes out bit for bit as a refit would compute it (two launches, one of them with a = x_new,
@@ -354,12 +411,11 @@ class GaussianProcess(Estimator):
 		self._xd = xd_all
 		self._yd = torch.cat((self._yd, yd_new.reshape(-1, 1)), dim=0)
 		self.fitted = False
-		self._alpha_cache = self._Lr = self._winvr = None
-		self._L = self._Lbuf = self._winv = self._z = None
+		self._factor = None
 		info = _lib.potrf_append(buf, n0, winv, z, yd_new)
 		self._check_info(info)
 		_lib.check_async("add_data_point: stpy_potrf_append")
-		self._Lbuf, self._L, self._winv, self._z = buf, buf[:n1p, :n1p], winv, z
+		self._factor = ResidentFactor(buf[:n1p, :n1p], winv, n1, z=z, key=key, buf=buf)
 		self.fitted = True
 		return True
 
@@ -529,15 +585,9 @@ class GaussianProcess(Estimator):
 		mu, sigma, X = self._predict(xt)
 		return mu, sigma, (xt, X, sigma)
 
-	def _reversed_factor(self):
-		"""J L^T J and its inverse diagonal blocks for B L^-1 (stpy_trsm_ln_factor): another N x N matrix, built once per fit."""
-		if getattr(self, "_Lr", None) is None:
-			self._Lr, self._winvr = _lib.trsm_ln_factor(self._L, self._winv)
-		return self._Lr, self._winvr
-
 	def _weights_t(self, X):
 		"""W^T = K* K^-1 = X L^-1 (in place over a copy of X): the variance gradient's coefficients, (mp, npad)."""
-		Lr, winvr = self._reversed_factor()
+		Lr, winvr = self._factor.reversed()                              # built by the first variance gradient after a fit
 		W = X.clone()
 		_lib.trsm_right_ln(W, Lr, winvr, self.nb, workspace=True)
 		return W
@@ -607,38 +657,23 @@ class GaussianProcess(Estimator):
 		problem over the stacked points (the objective is a sum of independent terms), so every step is one batched device
 		evaluation of the values and their analytic gradients.  Returns (solution, value) of the best start.
 		"""
-		from scipy.optimize import minimize
 		if self.bounds is None:
 			raise ValueError("ucb_optimize needs box bounds: set GaussianProcess.bounds to a list of (low, high) per coordinate")
-		mybounds = self.bounds
-		starts = []
-		for _ in range(multistart):
-			x0 = np.random.randn(self.d)
-			for i in range(self.d):
-				x0[i] = np.random.uniform(mybounds[i][0], mybounds[i][1])
-			starts.append(x0)
-		S, d = len(starts), self.d
+		starts = _draw_starts(multistart, self.d, self.bounds)
 		sign = -1.0 if lcb else 1.0
 		sb = float(np.sqrt(beta))
 		dev = self._xd.device if self._xd is not None else _lib.device()
 		dtype = self._xd.dtype if self._xd is not None else torch.float64
 
-		def evaluate(z):
-			xt = torch.from_numpy(np.ascontiguousarray(z.reshape(S, d))).to(device=dev, dtype=dtype)
+		def value(xt):
 			mu, sigma, state = self._posterior(xt)
-			val = mu + sign * sb * sigma
-			return val, state
+			return mu + sign * sb * sigma, state
 
-		def fun(z):
-			val, state = evaluate(z)
-			g = self._posterior_grad(state, torch.ones_like(val), torch.full_like(val, sign * sb))
-			return -float(val.sum().item()), -g.double().cpu().numpy().reshape(-1)
+		def evaluate(xt):
+			val, state = value(xt)
+			return val, self._posterior_grad(state, torch.ones_like(val), torch.full_like(val, sign * sb))
 
-		res = minimize(fun, np.concatenate(starts), method="L-BFGS-B", jac=True, bounds=list(mybounds) * S,
-					   options=dict(maxiter=15000, ftol=1e-15, gtol=1e-10))
-		sol = res.x.reshape(S, d)
-		vals, _ = evaluate(res.x)
-		vals = vals.double().cpu().numpy()
+		sol, vals, _ = _multistart_maximize(evaluate, starts, self.bounds, dev, dtype, final=lambda xt: value(xt)[0])
 		index = int(np.argmax(vals))
 		return (torch.from_numpy(sol[index].copy()), torch.tensor(float(vals[index]), dtype=torch.float64))
 
@@ -738,23 +773,18 @@ class GaussianProcess(Estimator):
 			self._xd = _lib.to_device(self.x)
 			self._yd = _lib.to_device(self.y, self._xd.dtype).reshape(-1, 1)
 			self.n = self._xd.shape[0]
-		reuse = (self.fitted and (not X) and (kernel is self.kernel_object) and self._Sigma is None
-				 and getattr(self, "_factor_key", None) == self._hyper_key(kernel))
-		if reuse:
-			L, winv, z = self._L, self._winv, self._z
-		else:
-			saved = self.kernel_object
-			self.kernel_object = kernel
-			try:
-				L, winv = self._factor(self._xd, X, None)
-			finally:
-				self.kernel_object = saved
-			z = _lib.trsv(L, winv, self._yd)
-		out2 = _lib.logdet_quad(L, z)
+		F = self._factor
+		if not (self.fitted and F is not None and (not X) and (kernel is self.kernel_object) and self._Sigma is None
+				and F.key == self._hyper_key(kernel)):
+			F, info = self._factorize(kernel, self._xd, X)                  # a factor of this call alone: the resident one stays
+			self._check_info(info)
+			F.z = _lib.trsv(F.L, F.winv, self._yd)
+		L = F.L
+		out2 = _lib.logdet_quad(L, F.z)
 		w = float(weight) if not torch.is_tensor(weight) else float(weight.item())
 		logdiag, quad = out2.tolist()                                                   # sum log L_ii, z^T z: host scalars
 		val = torch.full((1, 1), 0.5 * quad + 0.5 * w * 2.0 * logdiag, dtype=L.dtype, device=L.device)
-		return _lib.like_input(val, self.x), (L, winv, z)
+		return _lib.like_input(val, self.x), F
 
 	def _log_marginal_grads(self, kernel, X, weight, state, params):
 		"""
@@ -770,8 +800,8 @@ class GaussianProcess(Estimator):
 		against [Xs | 1].
 		"""
 		from ..kernels import _dev_const
-		L, winv, z = state
-		npad = L.shape[0]                               # tile-padded order of the factor (see _factor)
+		L, winv, z = state.L, state.winv, state.z
+		npad = L.shape[0]                               # tile-padded order of the factor (see _factorize)
 		items = kernel._resolve(dict(X) if X else {})
 		w = float(weight) if not torch.is_tensor(weight) else float(weight.item())
 		xd = self._xd

@@ -56,25 +56,7 @@ import torch
 
 from .. import _lib
 from ..kernels import KernelFunction
-from .gauss_procc import GaussianProcess, _wants_grad
-
-
-class _FeaturePosteriorFn(torch.autograd.Function):
-	"""Autograd node of KernelizedFeatures.mean_std for a test tensor with requires_grad: forward = the HIP prediction, backward =
-	one stpy_rff_grad launch with C_t = g_mu_t theta + (g_sigma_t / sigma_t) Phi_t Z (the Z half only when g_sigma is nonzero)."""
-
-	@staticmethod
-	def forward(ctx, kf, xtest):
-		ctx.set_materialize_grads(False)
-		mu, std, state = kf._posterior(xtest.detach())
-		ctx.kf, ctx.state, ctx.like = kf, state, (xtest.device, xtest.dtype, tuple(xtest.shape))
-		return _lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(std.reshape(-1, 1), xtest)
-
-	@staticmethod
-	def backward(ctx, gmu, gstd):
-		dev, dt, shape = ctx.like
-		g = ctx.kf._posterior_grad(ctx.state, gmu, gstd)
-		return None, g.to(device=dev, dtype=dt).reshape(shape)
+from .gauss_procc import GaussianProcess, ResidentFactor, _PosteriorFn, _draw_starts, _multistart_maximize, _wants_grad
 
 
 class KernelizedFeatures(GaussianProcess):
@@ -118,11 +100,10 @@ class KernelizedFeatures(GaussianProcess):
 		self.nb = 0
 		self.slab_bytes = 2 << 30          # features held at a time while V and Phi^T y are accumulated (fit_gp)
 		self._xd = self._yd = None
-		self._L = self._winv = self._z = self._Sigma = self._alpha_cache = None     # (the exact-GP factor of the base class: unused)
-		self._Lf = self._winvf = self._u = self._theta = None     # factor of V (primal, m x m) or K (dual, n x n); u = L^-1 rhs
+		self._Sigma = None
+		self._factor = self._theta = None                         # ResidentFactor of V (primal, m x m) or K (dual, n x n); z = L^-1 rhs
 		self._Vacc = self._rhs = self._part = None                # accumulated Phi^T Phi (lower tiles) and Phi^T y
 		self._PhiT = None                                         # dual form: Phi^T (m, n), kept (n < m)
-		self._inv_cache = None                                    # (factor, its inverse): V^-1 / K^-1 of the variance gradient
 
 	# ------------------------------------------------------------------ small API mirrors
 	def description(self):
@@ -175,7 +156,7 @@ class KernelizedFeatures(GaussianProcess):
 		"""kernelized_features.py:99-101: logdet(self.K) - logdet(s^2 lam I_m)."""
 		self.precompute()
 		m = self.get_basis_size()
-		ld = 2.0 * float(_lib.logdet_quad(self._Lf)[0].item()) if (self.dual and self.fitted) else 0.0        # primal: K is the ones(1, 1) placeholder
+		ld = 2.0 * float(_lib.logdet_quad(self._L)[0].item()) if (self.dual and self.fitted) else 0.0        # primal: K is the ones(1, 1) placeholder
 		return torch.tensor(ld - m * math.log(float(self.s) ** 2 * float(self.lam)), dtype=torch.float64)
 
 	def effective_dim(self, xtest):
@@ -205,7 +186,7 @@ class KernelizedFeatures(GaussianProcess):
 			self.precompute()
 			m = self.get_basis_size()
 			c = float(self.s) ** 2 * float(self.lam)
-			ldV = 2.0 * float(_lib.logdet_quad(self._Lf)[0].item()) + ((m - self.n) * math.log(c) if self.dual else 0.0)
+			ldV = 2.0 * float(_lib.logdet_quad(self._L)[0].item()) + ((m - self.n) * math.log(c) if self.dual else 0.0)
 			val = float(self.bound) * float(self.lam) + ldV - m * math.log(float(self.s) ** 2) - m * math.log(float(self.lam)) + 2 * np.log(1 / delta)
 			return torch.tensor(val, dtype=torch.float64)
 		return self.beta_fun(self.K, delta=delta, norm=norm)
@@ -244,7 +225,7 @@ class KernelizedFeatures(GaussianProcess):
 		self.fitted = False
 		self.to_add = []
 		self._Vacc = self._rhs = self._part = self._PhiT = None
-		self._Lf = self._winvf = self._u = self._theta = None
+		self._factor = self._theta = None
 		self.precompute()
 		return None
 
@@ -319,7 +300,7 @@ class KernelizedFeatures(GaussianProcess):
 			r0 += take
 			del PhiT
 
-	def _chol(self, A, what, keep=None):
+	def _chol(self, A, what):
 		"""In-place stpy_potrf of A; returns (A, winv).  Raises LinAlgError (and leaves the object unfitted) on a failing pivot."""
 		winv, info = _lib.potrf(A, self.nb)
 		self._check_info(info, "KernelizedFeatures: " + what + " is not positive definite (leading minor %d)")
@@ -331,11 +312,10 @@ class KernelizedFeatures(GaussianProcess):
 		# V = V_acc, then + s^2 lam on the diagonal (one pass of the elementwise kernel)
 		_lib.combine(V, self._Vacc, _lib.OUT_SET, float(self.s) ** 2 * float(self.lam))
 		self.fitted = False
-		L, winv = self._chol(V, "Phi^T Phi + s^2 lam I")
-		u = _lib.trsv(L, winv, self._rhs)
-		theta = _lib.trsv(L, winv, u, trans=1)
+		F = ResidentFactor(*self._chol(V, "Phi^T Phi + s^2 lam I"))
+		theta = F.solve(self._rhs)
 		_lib.check_async("KernelizedFeatures: stpy_trsv")           # a hand-off wait that gave up has poisoned u / theta with NaN
-		self._Lf, self._winvf, self._u, self._theta = L, winv, u, theta
+		self._factor, self._theta = F, theta
 		self.fitted = True
 
 	def _dual_K(self):
@@ -354,13 +334,12 @@ class KernelizedFeatures(GaussianProcess):
 			PhiT = PhiT.contiguous()
 		self._PhiT = PhiT
 		self.fitted = False
-		L, winv = self._chol(self._dual_K(), "Phi Phi^T + s^2 lam I")
-		z = _lib.trsv(L, winv, yd)
-		alpha = _lib.trsv(L, winv, z, trans=1)
+		F = ResidentFactor(*self._chol(self._dual_K(), "Phi Phi^T + s^2 lam I"))
+		alpha = F.solve(yd)
 		_lib.check_async("KernelizedFeatures: stpy_trsv")           # a hand-off wait that gave up has poisoned z / alpha with NaN
 		theta = torch.empty((PhiT.shape[0],), dtype=PhiT.dtype, device=PhiT.device)
 		_lib.predict(PhiT, alpha, theta)                                  # theta = Phi^T alpha
-		self._Lf, self._winvf, self._u, self._theta = L, winv, z, theta
+		self._factor, self._theta = F, theta
 		self.fitted = True
 
 	# ------------------------------------------------------------------ V, V^-1
@@ -390,7 +369,7 @@ class KernelizedFeatures(GaussianProcess):
 			V = self._V_device()
 			L, winv = self._chol(V, "V (dual get_invV)")
 			return _lib.potri(L, winv)
-		return _lib.potri(self._Lf, self._winvf)
+		return _lib.potri(self._L, self._winv)                           # a matrix of the caller's own (sample_theta factors it in place)
 
 	@property
 	def invV(self):
@@ -417,10 +396,10 @@ class KernelizedFeatures(GaussianProcess):
 			Z = float(self.s) ** 2 * self.invV                       # (host-side scale of a returned matrix, as :257)
 			return (theta, Z)
 		# dual: Z = invK_V = (I - Q^T K^-1 Q) / lam = (I - W W^T) / lam with W = Q^T L^-T  (m x n)
-		L = self._Lf
+		L = self._L
 		m = self._PhiT.shape[0]
 		W = self._PhiT.clone()
-		_lib.trsm_right_lt(W, L, self._winvf, self.nb)
+		_lib.trsm_right_lt(W, L, self._winv, self.nb)
 		Z = torch.eye(m, dtype=L.dtype, device=L.device)
 		_lib.gemm_nt(W, W, Z, 1)
 		if float(self.lam) != 1.0:
@@ -435,14 +414,14 @@ class KernelizedFeatures(GaussianProcess):
 	def mean_std(self, xtest):
 		"""kernelized_features.py:269-288.  A test tensor with requires_grad gets a graph (the input gradients of the module header)."""
 		if _wants_grad(xtest):
-			return _FeaturePosteriorFn.apply(self, xtest)
+			return _PosteriorFn.apply(self, xtest)
 		mu, std, _ = self._posterior(xtest)
 		return (_lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(std.reshape(-1, 1), xtest))
 
 	def _posterior(self, xtest):
 		"""mu, std (M,) on the device and what their input gradient needs: (xt, Phi, std)."""
 		self.precompute()
-		L = self._Lf
+		L, winv, u = self._L, self._winv, self._z
 		xt = _lib.to_device(xtest, L.dtype)
 		Phi = _lib.to_device(self.embedding.embed(xt), L.dtype)          # (M, m): rows = right-hand sides
 		if Phi.stride(1) != 1:
@@ -452,8 +431,8 @@ class KernelizedFeatures(GaussianProcess):
 		std = torch.empty_like(ss)
 		if not self.dual:
 			X = Phi.clone()
-			_lib.trsm_right_lt(X, L, self._winvf, self.nb)
-			_lib.predict(X, self._u, mu, ss, clamp=2)
+			_lib.trsm_right_lt(X, L, winv, self.nb)
+			_lib.predict(X, u, mu, ss, clamp=2)
 			# std = s sqrt(ss) = sqrt(0 - (-s^2) ss): the prediction epilogue with a zero prior term (no torch arithmetic on the vectors)
 			_lib.predict_finish(sumsq=ss, kdiag=torch.zeros_like(ss), scale=-float(self.s) ** 2, sigma=std)
 			return mu, std, (xt, Phi, std)
@@ -462,8 +441,8 @@ class KernelizedFeatures(GaussianProcess):
 		n = PhiTr.shape[0]
 		X = torch.empty((M, n), dtype=L.dtype, device=L.device)
 		_lib.gemm_nt(Phi, PhiTr, X)
-		_lib.trsm_right_lt(X, L, self._winvf, self.nb)
-		_lib.predict(X, self._u, mu, ss, clamp=2)
+		_lib.trsm_right_lt(X, L, winv, self.nb)
+		_lib.predict(X, u, mu, ss, clamp=2)
 		kd = torch.empty_like(ss)                                         # |phi*|^2: the same row-sum kernel on Phi*
 		_lib.predict(Phi, self._theta, sigma=kd, clamp=2)
 		_lib.predict_finish(sumsq=ss, kdiag=kd, scale=1.0, sigma=std, clamp=1 if self.clamp_variance else 0)
@@ -474,15 +453,9 @@ class KernelizedFeatures(GaussianProcess):
 	mean_var = mean_std
 
 	# ------------------------------------------------------------------ input gradients (kernelized_features.py:441-535)
-	def _factor_inverse(self):
-		"""V^-1 (primal) / K^-1 (dual), full symmetric, from the resident factor: one stpy_potri per fit."""
-		if self._inv_cache is None or self._inv_cache[0] is not self._Lf:
-			self._inv_cache = (self._Lf, _lib.potri(self._Lf, self._winvf))
-		return self._inv_cache[1]
-
 	def _phi_z(self, Phi):
 		"""(Phi Z up to its scalar, the scalar): Z = s^2 V^-1 (primal), (I - Phi_train^T K^-1 Phi_train) / lam (dual).  (M, m)."""
-		inv = self._factor_inverse()
+		inv = self._factor.inverse()                                      # V^-1 (primal) / K^-1 (dual): one stpy_potri per fit
 		if not self.dual:
 			out = torch.empty_like(Phi)
 			_lib.gemm_nt(Phi, inv, out)                                   # V^-1 is symmetric: Phi V^-1 = Phi (V^-1)^T
@@ -547,32 +520,8 @@ class KernelizedFeatures(GaussianProcess):
 		"""Gradient (M, d) and Hessian (M, d, d) of the posterior mean at every row of xtest (the order-2 path of stpy_rff_grad; the
 		reference's mean_gradient_hessian(x, hessian=True), :441-456, is row 0 of this)."""
 		self.precompute()
-		_, G, H = self._value_grad(_lib.to_device(xtest, self._Lf.dtype), self._theta.reshape(-1).contiguous(), hessian=True)
+		_, G, H = self._value_grad(_lib.to_device(xtest, self._L.dtype), self._theta.reshape(-1).contiguous(), hessian=True)
 		return _lib.like_input(G, xtest), _lib.like_input(H, xtest)
-
-	def _multistart_maximize(self, evaluate, starts, bounds):
-		"""All starts as ONE L-BFGS-B problem over the stacked points (the objective is a sum of independent terms; the pattern of
-		GaussianProcess.ucb_optimize): ``evaluate`` maps device points (S, d) to (values (S,), gradients (S, d)), one batched device
-		evaluation per step.  Returns (solutions (S, d), values (S,), number of evaluations) as NumPy float64."""
-		from scipy.optimize import minimize
-		S, d = len(starts), len(starts[0])
-		dev = _lib.device()
-		dtype = self._Lf.dtype if self._Lf is not None else torch.float64
-		count = [0]
-
-		def run(z):
-			count[0] += 1
-			xt = torch.from_numpy(np.ascontiguousarray(z.reshape(S, d))).to(device=dev, dtype=dtype)
-			return evaluate(xt)
-
-		def fun(z):
-			val, g = run(z)
-			return -float(val.sum().item()), -g.double().cpu().numpy().reshape(-1)
-
-		res = minimize(fun, np.concatenate(starts), method="L-BFGS-B", jac=True, bounds=list(bounds) * S,
-					   options=dict(maxiter=15000, ftol=1e-15, gtol=1e-10))
-		vals, _ = run(res.x)
-		return res.x.reshape(S, d), vals.double().cpu().numpy(), count[0]
 
 	def sample_and_optimize(self, xtest=None, multistart=25, minimizer="L-BFGS-B", grid=100, verbose=0):
 		"""
@@ -586,16 +535,11 @@ class KernelizedFeatures(GaussianProcess):
 			mybounds = tuple([(-self.diameter, self.diameter) for _ in range(self.d)])
 		else:
 			mybounds = self.bounds
-		starts = []
-		for _ in range(multistart):
-			x0 = np.random.randn(self.d)
-			for i in range(self.d):
-				x0[i] = np.random.uniform(mybounds[i][0], mybounds[i][1])
-			if minimizer != "L-BFGS-B":
-				raise AssertionError("Wrong optimizer selected.")
-			starts.append(x0)
+		if minimizer != "L-BFGS-B":
+			raise AssertionError("Wrong optimizer selected.")
+		starts = _draw_starts(multistart, self.d, mybounds)
 		row = thT.reshape(-1).contiguous()
-		sol, vals, evals = self._multistart_maximize(lambda xt: self._value_grad(xt, row), starts, mybounds)
+		sol, vals, evals = _multistart_maximize(lambda xt: self._value_grad(xt, row), starts, mybounds, _lib.device(), row.dtype)
 		self._last_optimize_evaluations = evals
 		if verbose:
 			print("sample_and_optimize: %d starts, %d device evaluations" % (len(starts), evals))
@@ -603,7 +547,7 @@ class KernelizedFeatures(GaussianProcess):
 		return (torch.from_numpy(sol[index].copy()), torch.from_numpy(vals[index:index + 1].copy()))
 
 	# These four names of GaussianProcess stay refused for now: the machinery above serves them (``_posterior_grad`` is mean_std_grad,
-	# ``_mean_hessian`` is mean_gradient_hessian, ``_multistart_maximize`` with ``_posterior`` + ``_posterior_grad`` is ucb_optimize),
+	# ``_mean_hessian`` is mean_gradient_hessian, gauss_procc's ``_multistart_maximize`` with ``_posterior`` + ``_posterior_grad`` is ucb_optimize),
 	# and the inherited methods would differentiate the kernel-space posterior, i.e. return numbers of the wrong model.
 	def _no_input_gradients(self, *args, **kwargs):
 		raise NotImplementedError("KernelizedFeatures does not expose mean_std_grad, mean_gradient_hessian, gradient_mean_var and ucb_optimize "
@@ -652,7 +596,7 @@ class KernelizedFeatures(GaussianProcess):
 		self.precompute()
 		if not (self.fitted == True and prior == False):
 			dev = _lib.device()
-			dtype = self._Lf.dtype if self._Lf is not None else torch.float64
+			dtype = self._L.dtype if self._L is not None else torch.float64
 			return self._prior_theta_t(random_vector, dtype, dev)
 		# L = chol(get_invV()) * s, theta = theta_mean + L r  (:328-330).  theta^T = 1 theta_mean^T + (s r)^T L^T: the accumulating
 		# NT product of the scaled draw (size x basis) with the lower-triangular factor

@@ -390,6 +390,44 @@ def test_gpu_estimator_against_reference(gpu_device, case):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("primal", [True, False])
+def test_gpu_sigma_gradient_after_refit(gpu_device, primal):
+	"""The sigma-gradient reads V^-1 (primal) / K^-1 (dual), built once per factor by the first gradient after a fit.  Model A takes a
+	gradient (which fills that inverse), then gets 3 queued points and takes the gradient again; model B gets the same fit and the
+	same points and only then its first gradient.  Both final factors come from the same launches on the same data and the library's
+	reductions are fixed-order, so the two gradients are equal bit for bit; an inverse that outlived A's first factor would differ
+	in the first digit.  m = 64 features, 40 + 3 points: primal=False stays in the dual form (43 < 64)."""
+	import stpy_amd
+	from stpy_amd.continuous_processes.kernelized_features import KernelizedFeatures
+	rng = np.random.RandomState(21)
+	x = rng.uniform(-1, 1, size=(43, 2))
+	y = np.sin(3 * x[:, :1]) * np.cos(2 * x[:, 1:]) + 0.05 * rng.normal(size=(43, 1))
+	x, y, xt = torch.from_numpy(x), torch.from_numpy(y), torch.from_numpy(rng.uniform(-1, 1, size=(5, 2)))
+	np.random.seed(8)
+	emb = stpy_amd.RFFEmbedding(gamma=0.5, m=64, d=2)
+
+	def model():
+		KF = KernelizedFeatures(embedding=emb, m=emb.get_m(), s=0.1, lam=1.0, d=2, primal=primal)
+		KF.fit_gp(x[:40], y[:40])
+		return KF
+
+	def sigma_grad(KF):
+		z = xt.clone().requires_grad_(True)
+		KF.mean_std(z)[1].sum().backward()
+		return z.grad
+
+	A, B = model(), model()
+	before = sigma_grad(A)
+	for KF in (A, B):
+		KF.add_data_point(x[40:], y[40:])
+		assert KF.fitted is False                                 # queued: folded in by the next prediction
+	gA, gB = sigma_grad(A), sigma_grad(B)
+	assert A.n == B.n == 43 and A.dual == B.dual == (not primal)
+	assert bool(torch.isfinite(gA).all()) and not torch.equal(gA, before)
+	assert torch.equal(gA, gB), float((gA - gB).abs().max() / gB.abs().max())
+
+
+@pytest.mark.gpu
 def test_gpu_quadrature_derivatives(gpu_device):
 	import stpy_amd
 	g = golden("G18_kf_input_grad")

@@ -57,7 +57,7 @@ def main():
 	winv[:GP._winv.numel()] = GP._winv
 	z = torch.zeros((cap,), dtype=torch.float64, device=dev)
 	z[:n0] = GP._z[:n0]
-	GP._L = GP._winv = GP._alpha_cache = None
+	GP._factor = None
 	torch.cuda.empty_cache()
 	rows = torch.empty((kmax, n0 + kmax), dtype=torch.float64, device=dev)
 	GP.kernel_object._kernel_into(x[:n0 + kmax], x[n0:].contiguous(), rows)

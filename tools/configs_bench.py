@@ -51,7 +51,7 @@ def c3():
 	print("C3  N=65536 d=16 Matern-5/2 fp32 fit+mean_std+log_marginal: %.4f s  %.1f TFLOP/s  (lml %.4f, nan=%s)" % (t, F / t / 1e12, float(lml), bool(torch.isnan(std).any())), flush=True)
 	# residual check of the fp32 factorisation on a probe vector: || K alpha - y || / || y ||
 	A = gp.A
-	del gp._L
+	gp._factor = None
 	torch.cuda.empty_cache()
 	K = gp.K
 	r = K @ A - y

@@ -94,8 +94,8 @@ def estimator_part(dev):
 	both()                                        # V^-1 once per fit (stpy_potri), outside the timed window
 	torch.cuda.synchronize()
 	t0 = time.perf_counter()
-	KF._inv_cache = None
-	KF._factor_inverse()
+	KF._factor._inverse = None
+	KF._factor.inverse()
 	torch.cuda.synchronize()
 	print("V^-1 (stpy_potri, once per fit) m=%d: %.1f ms" % (m, (time.perf_counter() - t0) * 1e3))
 	(tf, tfm), (tb, tbm), (tm, tmm) = event_ms([forward, both, mean_only], reps=5)

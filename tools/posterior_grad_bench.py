@@ -62,8 +62,8 @@ def main():
 	gp.mean_std_grad(xt[:8])                     # builds the reversed factor once (per fit)
 	torch.cuda.synchronize()
 	t0 = time.perf_counter()
-	gp._Lr = gp._winvr = None
-	gp._reversed_factor()
+	gp._factor._reversed = None
+	gp._factor.reversed()
 	torch.cuda.synchronize()
 	print("reversed factor (stpy_trsm_ln_factor) N=%d: %.2f ms" % (n, (time.perf_counter() - t0) * 1e3), flush=True)
 	ts, tsm = timed(lambda: gp.mean_std(xt), reps=3)
