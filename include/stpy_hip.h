@@ -152,6 +152,32 @@ int64_t stpy_potrf_append_workspace_bytes(int dtype, int64_t n0, int64_t k);
 int stpy_potrf_append(int dtype, int64_t n0, int64_t k, void* A, int64_t lda, void* winv, int64_t winv_elems, void* z, const void* y,
                       void* work, int64_t work_bytes, int32_t* info_dev, void* stream);
 
+/*
+ * Rank-k update (sign = +1) or downdate (sign = -1) of a resident factor in place: KernelizedFeatures.add_data_point(iterative=True),
+ * the feature-space counterpart of the bordered factor above (the reference's rank-one Woodbury step on the explicit inverse,
+ * kernelized_features.py:213-218).
+ *   on entry: the lower triangle of L (n x n, any n >= 1) holds a factor as stpy_potrf leaves it, winv its inverse 128 x 128 diagonal
+ *             blocks; W is n x k row-major, ldw >= k (the (m, k) tensor embed_t returns); sign is +1 or -1.
+ *   on exit:  L' L'^T = L L^T + sign W W^T with a positive diagonal; EVERY block of winv is refreshed, in the layout stpy_potrf
+ *             leaves for the new matrix (identity on the rows / columns of a ragged last tile), so every consumer -- stpy_trsv,
+ *             stpy_trsm_right_lt, stpy_potri, stpy_logdet_quad -- runs on (L', winv) unchanged; W is destroyed; the strict upper
+ *             triangle of L is neither read nor written; *info_dev = 0, or the 1-based index of the first column whose pivot is not
+ *             positive and finite (sign = -1: l_jj^2 - w_j^2 <= 0) -- L is then undefined from that column on and the caller refits.
+ * W^T is eliminated against L^T column by column with plane rotations (hyperbolic for sign = -1), all k columns of a chunk of W
+ * against column j before column j + 1, in block columns of 128: one workgroup rotates the diagonal block and writes the table of
+ * (c, s, 1/c) into `work`, a second launch applies it to the rows below (one row per lane, staged through LDS).  32 columns of W ride
+ * along in one pass over L; a wider W is cut into chunks inside the call, each a pass of its own.  One pass reads and writes the
+ * lower triangle once: O(n^2 k) work against the O(n^3) of a refactorisation.  Every sum has a fixed order: bit-reproducible.
+ * Refused: dtype (-1), n < 0 (-2), k < 0 (-3), sign (-4), NULL L / winv / W / work / info_dev (-5 / -7 / -9 / -11 / -13), ldl < n (-6),
+ * ldw < k (-10), winv_elems < stpy_potrf_winv_elems(n) (-21), work_bytes < the query (-20).  n == 0 or k == 0: returns 0, nothing is
+ * read or written.
+ */
+int64_t stpy_chol_update_workspace_bytes(int dtype, int64_t n, int64_t k);
+int stpy_chol_update(int dtype, int64_t n, int64_t k, int sign,
+                     void* L, int64_t ldl, void* winv, int64_t winv_elems,
+                     void* W, int64_t ldw,
+                     void* work, int64_t work_bytes, int32_t* info_dev, void* stream);
+
 /* B <- B L^-T for B: m x n row-major (rows = right-hand sides).  With B = K* (M x N) this is
  * V^T = (L^-1 K*^T)^T of the variance term, gauss_procc.py:378,392.  From 2048 rows on: recursive
  * halving of the column range (one long product per split, no workspace).  Fewer rows: panels of nb

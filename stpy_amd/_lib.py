@@ -39,6 +39,8 @@ SIGNATURES = {
 	"stpy_potrf": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp]),
 	"stpy_potrf_append_workspace_bytes": (_i64, [_i32, _i64, _i64]),
 	"stpy_potrf_append": (_i32, [_i32, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+	"stpy_chol_update_workspace_bytes": (_i64, [_i32, _i64, _i64]),
+	"stpy_chol_update": (_i32, [_i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
 	"stpy_trsm_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32]),
 	"stpy_trsm_right_lt": (_i32, [_i32, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
 	"stpy_potri": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -273,6 +275,16 @@ def potrf_append(A, n0, winv, z, y):
 	work = _work(max(int(load().stpy_potrf_append_workspace_bytes(dtype_code(A.dtype), n0, k)), 1), A)
 	info = torch.zeros((1,), dtype=torch.int32, device=A.device)
 	_launch("stpy_potrf_append", dtype_code(A.dtype), n0, k, ptr(A), ld(A), ptr(winv), winv.numel(), ptr(z), ptr(y), ptr(work), work.numel(), ptr(info))
+	return info
+
+
+def chol_update(L, winv, W, sign=1):
+	"""Rank-k update (sign = +1) or downdate (-1) of a factor in place: L L^T + sign W W^T, winv refreshed (stpy_chol_update in the header).
+	W, (n, k) with rows of k contiguous elements, is destroyed.  Returns the unread status word, as potrf."""
+	n, k = L.shape[0], W.shape[1]
+	work = _work(max(int(load().stpy_chol_update_workspace_bytes(dtype_code(L.dtype), n, k)), 1), L)
+	info = torch.zeros((1,), dtype=torch.int32, device=L.device)
+	_launch("stpy_chol_update", dtype_code(L.dtype), n, k, int(sign), ptr(L), ld(L), ptr(winv), winv.numel(), ptr(W), ld(W), ptr(work), work.numel(), ptr(info))
 	return info
 
 

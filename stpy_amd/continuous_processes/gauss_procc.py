@@ -144,11 +144,13 @@ class ResidentFactor:
 	  n         order of the matrix that was factored (L's order without the padding)
 	  buf       the capacity buffer L is a leading view of after an append (room for more rows), else None
 	  z         L^-1 y; None on a factor nobody solved with
-	  key       GaussianProcess._hyper_key of the hyper-parameters it was built from, None where nothing compares it"""
+	  key       GaussianProcess._hyper_key of the hyper-parameters it was built from, None where nothing compares it
+	An estimator that modifies L in place (KernelizedFeatures: stpy_chol_update) resets the derived fields itself; ``_sampler`` is its
+	(chol((L L^T)^-1), inverse diagonal blocks) pair for the theta draws, None until the first draw."""
 
 	def __init__(self, L, winv, n=None, z=None, key=None, buf=None):
 		self.L, self.winv, self.n, self.z, self.key, self.buf = L, winv, L.shape[0] if n is None else n, z, key, buf
-		self._alpha = self._reversed = self._inverse = None
+		self._alpha = self._reversed = self._inverse = self._sampler = None
 
 	def solve(self, y):
 		"""z = L^-1 y, kept; returns alpha = L^-T z."""

@@ -24,15 +24,21 @@ That requires an embedding that acts ROW BY ROW (each output row depends on its 
     V = L L^T                           stpy_potrf  (the reference takes pinverse(V); V is SPD for s, lam > 0)
     theta                               stpy_trsv forward + backward
     X = Phi* L^-T, mean = X u, std      stpy_trsm_right_lt, stpy_predict, stpy_predict_finish
-    samplers                            stpy_potri -> stpy_potrf -> stpy_tril -> stpy_gemm_nt (chol(V^-1) s r, the reference's own factor
-                                        of the covariance, so a seeded run draws the same theta); Matheron: stpy_gram + stpy_potrf +
+    samplers                            stpy_potri -> stpy_potrf -> stpy_tril (once per factor) -> stpy_gemm_nt (chol(V^-1) s r, the reference's
+                                        own factor of the covariance, so a seeded run draws the same theta); Matheron: stpy_gram + stpy_potrf +
                                         stpy_trsm_right_lt + stpy_gemm_nt
 Standard-normal draws are taken exactly as the reference takes them (torch.normal on the CPU generator, shape (basis, size)).
 
 ``add_data_point`` queues points as the reference does (:108-113) and the next prediction folds them in: k new rows cost their
 embedding, one k-deep ``+=`` product and one m x m refactorisation (the reference's rank-one Woodbury / Schur updates of the
-explicit inverse, :181-221, call ``add_points`` with the wrong arity and raise).  The cvxpy / MOSEK constrained fits
-(:338-435) are outside the hot path.
+explicit inverse, :181-221, call ``add_points`` with the wrong arity and raise).  ``add_data_point(x, y, iterative=True)`` replaces
+the refactorisation by a rank-k update of the resident factor (``stpy_chol_update``, csrc/cholupdate.hip: V' = V + W W^T with
+W = Phi_new^T, one pass over L, O(m^2 k)) whenever every queued point asked for it, the primal form is active, a factor of the same
+dtype and the same s^2 lam is resident and the batch has at most ``update_max_rank`` rows; V_acc and Phi^T y are kept exact as on
+the refit path, theta is two ``stpy_trsv`` on the updated factor, and a failed update (status word, hand-off error) falls back to
+the refit of V_acc.  The sampler's factor chol(V^-1) is kept on the resident factor; a one-row update downdates it
+(V'^-1 = V^-1 - u u^T, u = V^-1 w / sqrt(1 + w^T V^-1 w): two ``stpy_trsv`` and ``stpy_chol_update`` with sign -1), a wider one
+drops it.  The cvxpy / MOSEK constrained fits (:338-435) are outside the hot path.
 
 Input gradients (csrc/rffgrad.hip).  Both forms have mu = phi^T theta and sigma^2 = phi^T Z phi with a symmetric Z (primal
 s^2 V^-1, dual (I - Phi^T K^-1 Phi) / lam), so for upstream gradients g_mu, g_sigma
@@ -99,10 +105,12 @@ class KernelizedFeatures(GaussianProcess):
 		self.kernel_object = None
 		self.nb = 0
 		self.slab_bytes = 2 << 30          # features held at a time while V and Phi^T y are accumulated (fit_gp)
+		self.update_max_rank = 128         # widest batch of add_data_point(iterative=True) that updates the factor instead of refitting
 		self._xd = self._yd = None
 		self._Sigma = None
 		self._factor = self._theta = None                         # ResidentFactor of V (primal, m x m) or K (dual, n x n); z = L^-1 rhs
 		self._Vacc = self._rhs = self._part = None                # accumulated Phi^T Phi (lower tiles) and Phi^T y
+		self._ridge = None                                        # s^2 lam the resident primal factor was built with
 		self._PhiT = None                                         # dual form: Phi^T (m, n), kept (n < m)
 
 	# ------------------------------------------------------------------ small API mirrors
@@ -192,12 +200,14 @@ class KernelizedFeatures(GaussianProcess):
 		return self.beta_fun(self.K, delta=delta, norm=norm)
 
 	# ------------------------------------------------------------------ fit
-	def add_data_point(self, x, y):
-		"""kernelized_features.py:108-113: the first point fits, later ones are queued and folded in by the next ``precompute``."""
+	def add_data_point(self, x, y, iterative=False):
+		"""kernelized_features.py:108-113: the first point fits, later ones are queued and folded in by the next ``precompute``.
+		``iterative=True`` asks that fold for a rank-k update of the resident factor instead of a refactorisation (see the module
+		header for when it is taken); entries queued without it keep the reference's [x, y] form."""
 		if self.n == 0:
 			self.fit_gp(x, y)
 		else:
-			self.to_add.append([x, y])
+			self.to_add.append([x, y, True] if iterative else [x, y])
 			self.fitted = False
 
 	add_data = add_data_point
@@ -235,6 +245,7 @@ class KernelizedFeatures(GaussianProcess):
 			return
 		if len(self.to_add) > 0 and self._Vacc is not None and not self.dual:
 			# primal: the accumulated normal equations are extended by the queued rows
+			iterative = all(len(p) > 2 and p[2] for p in self.to_add)
 			newx = torch.cat([p[0] for p in self.to_add], dim=0)
 			newy = torch.cat([p[1] for p in self.to_add], dim=0)
 			self.to_add = []
@@ -242,7 +253,14 @@ class KernelizedFeatures(GaussianProcess):
 			self.n = list(self.x.size())[0]
 			self._xd = self._yd = None
 			dtype = self._Vacc.dtype
-			self._accumulate(_lib.to_device(newx, dtype), _lib.to_device(newy, dtype).reshape(-1), first=False)
+			xn, yn = _lib.to_device(newx, dtype), _lib.to_device(newy, dtype).reshape(-1)
+			F = self._factor
+			if (iterative and F is not None and F.L.dtype == dtype and self._ridge == float(self.s) ** 2 * float(self.lam)
+					and 0 < xn.shape[0] <= int(self.update_max_rank)):
+				if self._update_factor(xn, yn):
+					return
+			else:
+				self._accumulate(xn, yn, first=False)
 			self._solve_normal_equations()
 			return
 		if len(self.to_add) > 0:
@@ -300,6 +318,43 @@ class KernelizedFeatures(GaussianProcess):
 			r0 += take
 			del PhiT
 
+	def _update_factor(self, xn, yn):
+		"""The k rows (xn, yn) folded into the resident primal factor by a rank-k update: V_acc += W W^T and rhs += W yn exactly as the
+		refit path does (W = Phi_new^T, (m, k), embedded once), L <- chol(L L^T + W W^T) in place (stpy_chol_update), z and theta from
+		two vector solves, the derived inverse / reversed factor dropped.  A resident sampler factor C = chol(V^-1) follows a one-row
+		update by the downdate V'^-1 = V^-1 - u u^T, u = L^-T p / sqrt(1 + p^T p), p = L^-1 w (the OLD factor); a wider update drops it,
+		as does a downdate whose status word is not 0.  Returns False -- V_acc and rhs are up to date, the factor is not -- when the
+		update reports a failing pivot or a hand-off error: the caller refits."""
+		F = self._factor
+		W = _lib.to_device(self._embed_t(xn), xn.dtype)                   # (m, k)
+		if W.stride(1) != 1:
+			W = W.contiguous()
+		_lib.syrk(W, self._Vacc, 2)
+		_lib.predict(W, yn, self._part)
+		_lib.combine(self._rhs, self._part, _lib.OUT_ADD)
+		U = None
+		if F._sampler is not None and W.shape[1] == 1:
+			p = _lib.trsv(F.L, F.winv, W)
+			q = _lib.trsv(F.L, F.winv, p, trans=1)
+			U = (q * torch.rsqrt(1.0 + _lib.trace_dot(u=p, v=p)[1])).reshape(-1, 1)          # (one scalar, on the device)
+		info = _lib.chol_update(F.L, F.winv, W, 1)                        # (W is scratch from here on)
+		info_c = None if U is None else _lib.chol_update(F._sampler[0], F._sampler[1], U, -1)
+		F._alpha = F._inverse = F._reversed = None
+		self.fitted = False
+		theta = F.solve(self._rhs)
+		ok = int(info.item()) == 0
+		try:
+			_lib.check_async("KernelizedFeatures: stpy_trsv")       # a hand-off wait that gave up has poisoned u / theta with NaN
+		except _lib.StpyHipError:
+			ok = False
+		if not ok:
+			return False
+		if info_c is None or int(info_c.item()) != 0:
+			F._sampler = None                                             # the next draw factors V^-1 afresh
+		self._theta = theta
+		self.fitted = True
+		return True
+
 	def _chol(self, A, what):
 		"""In-place stpy_potrf of A; returns (A, winv).  Raises LinAlgError (and leaves the object unfitted) on a failing pivot."""
 		winv, info = _lib.potrf(A, self.nb)
@@ -316,6 +371,7 @@ class KernelizedFeatures(GaussianProcess):
 		theta = F.solve(self._rhs)
 		_lib.check_async("KernelizedFeatures: stpy_trsv")           # a hand-off wait that gave up has poisoned u / theta with NaN
 		self._factor, self._theta = F, theta
+		self._ridge = float(self.s) ** 2 * float(self.lam)
 		self.fitted = True
 
 	def _dual_K(self):
@@ -600,9 +656,13 @@ class KernelizedFeatures(GaussianProcess):
 			return self._prior_theta_t(random_vector, dtype, dev)
 		# L = chol(get_invV()) * s, theta = theta_mean + L r  (:328-330).  theta^T = 1 theta_mean^T + (s r)^T L^T: the accumulating
 		# NT product of the scaled draw (size x basis) with the lower-triangular factor
-		invV = self._invV_device()
-		Lc, _ = self._chol(invV, "V^-1 (sample_theta)")
-		_lib.tril(Lc)
+		# (the factor of V^-1 is kept with the resident factor of V: potri -> potrf -> tril once per fit, downdated by a one-row update)
+		F = self._factor
+		if F._sampler is None:
+			Lc, winvc = self._chol(self._invV_device(), "V^-1 (sample_theta)")
+			_lib.tril(Lc)
+			F._sampler = (Lc, winvc)
+		Lc = F._sampler[0]
 		rt = (float(self.s) * random_vector).T.contiguous().to(device=Lc.device, dtype=Lc.dtype)          # (size, basis)
 		thT = torch.empty((size, basis), dtype=Lc.dtype, device=Lc.device)
 		thT.copy_(self._theta.reshape(1, basis).expand(size, basis))

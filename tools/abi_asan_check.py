@@ -16,7 +16,7 @@ import textwrap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "stpy_amd", "csrc")
-SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce", "grad", "append", "rffgrad"]
+SRCS = ["api", "gemm", "gemm_bf3p", "potrf", "solve", "gram", "rff", "reduce", "grad", "append", "rffgrad", "cholupdate"]
 
 CHILD = r'''
 import ctypes, sys
@@ -121,6 +121,21 @@ assert lib.stpy_potrf_append(0, 100, 40, P, 256, P, 128 * 128, P, P, P, 1 << 30,
 assert lib.stpy_potrf_append(0, 100, 40, P, 256, P, 1 << 20, P, P, P, 10, P, N) == -20, "potrf_append workspace too small"
 neg(lib.stpy_potrf_append(7, 100, 4, P, 256, P, 1 << 20, P, P, P, 1 << 30, P, N), "potrf_append unknown dtype")
 zero(lib.stpy_potrf_append_workspace_bytes(0, 0, 4), "potrf_append workspace query, n0 = 0")
+# ---- rank-k update of a factor (argument order: dtype, n, k, sign, L, ldl, winv, winv_elems, W, ldw, work, work_bytes, info, stream)
+assert lib.stpy_chol_update_workspace_bytes(0, 389, 5) > 0 and lib.stpy_chol_update_workspace_bytes(1, 389, 5) * 2 == lib.stpy_chol_update_workspace_bytes(0, 389, 5)
+zero(lib.stpy_chol_update_workspace_bytes(0, 389, 0), "chol_update workspace query, k = 0")
+neg(lib.stpy_chol_update(7, 256, 2, 1, P, 256, P, 1 << 20, P, 2, P, 1 << 30, P, N), "chol_update unknown dtype")
+neg(lib.stpy_chol_update(0, -1, 2, 1, P, 256, P, 1 << 20, P, 2, P, 1 << 30, P, N), "chol_update n < 0")
+neg(lib.stpy_chol_update(0, 256, 2, 0, P, 256, P, 1 << 20, P, 2, P, 1 << 30, P, N), "chol_update sign = 0")
+neg(lib.stpy_chol_update(0, 256, 2, 1, N, 256, P, 1 << 20, P, 2, P, 1 << 30, P, N), "chol_update null L")
+neg(lib.stpy_chol_update(0, 256, 2, 1, P, 200, P, 1 << 20, P, 2, P, 1 << 30, P, N), "chol_update ldl < n")
+neg(lib.stpy_chol_update(0, 256, 2, 1, P, 256, P, 1 << 20, N, 2, P, 1 << 30, P, N), "chol_update null W")
+neg(lib.stpy_chol_update(0, 256, 2, 1, P, 256, P, 1 << 20, P, 1, P, 1 << 30, P, N), "chol_update ldw < k")
+neg(lib.stpy_chol_update(0, 256, 2, 1, P, 256, P, 1 << 20, P, 2, P, 1 << 30, N, N), "chol_update null info")
+assert lib.stpy_chol_update(0, 257, 2, 1, P, 257, P, 2 * 128 * 128, P, 2, P, 1 << 30, P, N) == -21, "chol_update winv too small"
+assert lib.stpy_chol_update(0, 256, 2, -1, P, 256, P, 1 << 20, P, 2, P, 10, P, N) == -20, "chol_update workspace too small"
+zero(lib.stpy_chol_update(0, 256, 0, 1, N, 256, N, 0, N, 0, N, 0, N, N), "chol_update k = 0")
+zero(lib.stpy_chol_update(0, 0, 2, 1, N, 0, N, 0, N, 2, N, 0, N, N), "chol_update n = 0")
 # ---- RFF
 assert lib.stpy_rff_workspace_bytes(1, 262144, 64, 32768) > 0 and lib.stpy_rff_workspace_bytes(0, 100, 5, 64) == 0
 neg(lib.stpy_rff_embed(1, N, 16, 4, 4, P, 4, 8, N, N, 1.0, P, 8, 0, N, 0, N), "rff null x")
