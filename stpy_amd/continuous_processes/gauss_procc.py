@@ -97,6 +97,11 @@ def _wants_grad(xtest):
 	return torch.is_tensor(xtest) and xtest.requires_grad and torch.is_grad_enabled()
 
 
+def _weight(weight):
+	"""The evidence's log-det weight as a host float (a python number or a one-element tensor)."""
+	return float(weight.item()) if torch.is_tensor(weight) else float(weight)
+
+
 def _tile_pad(n):
 	"""Order at which an n x n SPD matrix is held on the device: the next multiple of the 128 x 128 GEMM tile."""
 	return -(-int(n) // 128) * 128
@@ -768,13 +773,17 @@ class GaussianProcess(Estimator):
 			out.append(("likelihood", "sigma", self.s))
 		return out
 
-	def _log_marginal_value(self, kernel, X, weight):
+	def _ensure_device_data(self, caller):
+		"""Data handed over by ``load_data`` goes to the device at its first use."""
 		if self._xd is None:
 			if self.x is None:
-				raise AttributeError("log_marginal needs data: call fit_gp or load_data first")
+				raise AttributeError("%s needs data: call fit_gp or load_data first" % caller)
 			self._xd = _lib.to_device(self.x)
 			self._yd = _lib.to_device(self.y, self._xd.dtype).reshape(-1, 1)
 			self.n = self._xd.shape[0]
+
+	def _log_marginal_value(self, kernel, X, weight):
+		self._ensure_device_data("log_marginal")
 		F = self._factor
 		if not (self.fitted and F is not None and (not X) and (kernel is self.kernel_object) and self._Sigma is None
 				and F.key == self._hyper_key(kernel)):
@@ -783,7 +792,7 @@ class GaussianProcess(Estimator):
 			F.z = _lib.trsv(F.L, F.winv, self._yd)
 		L = F.L
 		out2 = _lib.logdet_quad(L, F.z)
-		w = float(weight) if not torch.is_tensor(weight) else float(weight.item())
+		w = _weight(weight)
 		logdiag, quad = out2.tolist()                                                   # sum log L_ii, z^T z: host scalars
 		val = torch.full((1, 1), 0.5 * quad + 0.5 * w * 2.0 * logdiag, dtype=L.dtype, device=L.device)
 		return _lib.like_input(val, self.x), F
@@ -801,11 +810,10 @@ class GaussianProcess(Estimator):
 		sum_ij H_ij u_m^2 = 2 [ sum_i xs_im^2 h_i - xs_m^T H xs_m ] with h = H 1 -- one stpy_gemm_nt of H
 		against [Xs | 1].
 		"""
-		from ..kernels import _dev_const
 		L, winv, z = state.L, state.winv, state.z
 		npad = L.shape[0]                               # tile-padded order of the factor (see _factorize)
-		items = kernel._resolve(dict(X) if X else {})
-		w = float(weight) if not torch.is_tensor(weight) else float(weight.item())
+		items = kernel._chain(X)
+		w = _weight(weight)
 		xd = self._xd
 		n = xd.shape[0]
 		alpha = _lib.trsv(L, winv, z, trans=1)[:n]
@@ -829,9 +837,7 @@ class GaussianProcess(Estimator):
 					continue
 				premap = term['premap']
 				group = term['group']
-				identity = (group == list(range(xd.shape[1])))
-				cols = None if identity else _dev_const(group, None, xd.device, int32=True)
-				inv_ls = _dev_const(term['inv_ls'], xd.dtype, xd.device)
+				cols, inv_ls = kernel._term_operands(term, xd, xd.dtype, xd.device)
 				if premap is not None:
 					# full-covariance item (kernels.py:464-549): the points enter as z = x[:, group] cov with unit lengthscales; the
 					# parameter is the map itself.  d/dcov[a][m] = -1/2 sum_ij H_ij (z_i - z_j)_m (x_i - x_j)_a  (stpy_lml_grad_cov_reduce)
@@ -843,22 +849,8 @@ class GaussianProcess(Estimator):
 				# to `work` with K^-1 only read (no N x N copy)
 				H = Kinv if single else work
 				_lib.lml_weight(term['kind'], kx, inv_ls, term['kappa'], w, alpha, Kinv, H, cols=kcols)
-				# ... o M_i
-				factors = []
-				if it['op'] == "*" and i > 0:
-					factors.append(items[:i])
-				for j in range(i + 1, len(items)):
-					if items[j]['op'] == "*":
-						factors.append([items[j]])
-				for fac in factors:
-					if len(fac) == 1 and len(fac[0]['terms']) == 1:
-						# a single-term factor multiplies straight into H (STPY_OUT_MUL combine of stpy_gram)
-						kernel._run_items([dict(fac[0], op="*")], xd, xd, H, first_is_set=False)
-						continue
-					if tmp is None:
-						tmp = torch.empty((n, n), dtype=L.dtype, device=L.device)
-					kernel._run_items(fac, xd, xd, tmp)
-					_lib.combine(H, tmp, _lib.OUT_MUL)
+				# ... o M_i (a single-term factor multiplies straight into H; the scratch of the others is kept for the next term)
+				tmp = kernel._mul_factors_into(items, i, xd, xd, H, tmp)
 				# [Xs | 1]^T (dg + 1, n): scaled coordinates as the NT operand, then P = H [Xs | 1] and the per-coordinate sums (for the
 				# lengthscale sums the coordinates are taken relative to the first point: the sums do not see the translation, their
 				# rounding does; the full-covariance reduction works on the points as they are)
@@ -872,8 +864,7 @@ class GaussianProcess(Estimator):
 						raise ValueError("evidence gradient: 'cov' has %d entries, the item maps %d columns to %d" % (a_.numel(), len(group), dg))
 					_lib.lml_grad_cov_reduce(xd, kx, P, a_, cols)
 					continue
-				pidx = _dev_const([int(v) for v in term['pidx']], None, xd.device, int32=True)
-				_lib.lml_grad_reduce(xd, inv_ls, P, pidx, a_, cols, centred=True)
+				_lib.lml_grad_reduce(xd, inv_ls, P, kernel._term_param_slots(term, xd.device), a_, cols, centred=True)
 		del work, work_p
 		for key, name, t in wanted:
 			if (key, name) not in acc or int(key) >= len(items) or not any(tm['pname'] == name for tm in items[int(key)]['terms']):
@@ -941,13 +932,7 @@ class GaussianProcess(Estimator):
 		run one after another through ``log_marginal`` (``Estimator.log_marginal_batch``).  ``self.lml_batch_path`` says which:
 		"device" or "serial".
 		"""
-		if self._xd is None:
-			if self.x is None:
-				raise AttributeError("log_marginal_batch needs data: call fit_gp or load_data first")
-			self._xd = _lib.to_device(self.x)
-			self._yd = _lib.to_device(self.y, self._xd.dtype).reshape(-1, 1)
-			self.n = self._xd.shape[0]
-		from ..kernels import _dev_const
+		self._ensure_device_data("log_marginal_batch")
 		plan = self._lml_batch_plan(kernel, Xs)
 		if plan is None:
 			return super().log_marginal_batch(kernel, Xs, weight, s)
@@ -955,7 +940,7 @@ class GaussianProcess(Estimator):
 		xd = self._xd
 		B, d = inv_ls.shape
 		n_params = int(np.prod(shape))
-		w = float(weight) if not torch.is_tensor(weight) else float(weight.item())
+		w = _weight(weight)
 		noise = np.full(B, float(self.s)) if s is None else np.asarray([float(v) for v in s], dtype=np.float64)
 		if noise.shape[0] != B:
 			raise ValueError("log_marginal_batch: %d noise levels for %d candidates" % (noise.shape[0], B))
@@ -965,8 +950,7 @@ class GaussianProcess(Estimator):
 		host[B * d:B * d + B] = noise
 		host[B * d + B:].view(np.int32)[:d] = np.asarray(term['pidx'], dtype=np.int32)
 		dev = torch.from_numpy(host).to(xd.device)
-		group = term['group']
-		cols = None if group == list(range(xd.shape[1])) else _dev_const(group, None, xd.device, int32=True)
+		cols, _ = kernel._term_operands(term, xd, xd.dtype, xd.device)
 		_, _, _, packed = _lib.lml_batch(term['kind'], xd, self._yd.reshape(-1), dev[:B * d].view(B, d), dev[B * d:B * d + B],
 										 dev[B * d + B:].view(torch.int32)[:d], n_params, term['kappa'], w, cols=cols)
 		out = packed.cpu().numpy()          # the one read-back (waits for the launch)

@@ -281,61 +281,93 @@ class KernelFunction:
 		return _MATERN_KIND[nu]
 
 	# ------------------------------------------------------------------ evaluation
+	def _chain(self, kwargs=None, items=None):
+		"""The resolved items of the expression (or the given sub-chain ``items``), the first one's operation taken as "set"."""
+		if items is None:
+			items = self._resolve(dict(kwargs) if kwargs else {})
+		if items and items[0]['op'] != "-":
+			items = [dict(items[0], op="-")] + list(items[1:])
+		return items
+
 	@staticmethod
-	def _plan(items):
+	def _term_operands(term, x, dtype, device):
+		"""(cols, inv_ls) of a launch of ``term`` on the points x, on the device: cols is None where the term reads every column of x
+		in order -- also for x None: points that are the term's own coordinates already (pre-mapped), or that the launch does not read."""
+		group = term['group']
+		cols = None if x is None or group == list(range(x.shape[1])) else _dev_const(group, None, device, int32=True)
+		return cols, _dev_const(term['inv_ls'], dtype, device)
+
+	@staticmethod
+	def _term_param_slots(term, device):
+		"""pidx on the device: the entry of the term's hyper-parameter that sets each coordinate's lengthscale."""
+		return _dev_const([int(v) for v in term['pidx']], None, device, int32=True)
+
+	@staticmethod
+	def _launches(items, out, diag_add=0.0):
 		"""
-		Flattens the items into launches (term, target, combine).  An item is the SUM of its terms;
-		items are chained with the + / * algebra of kernels.py:146-157.  A multi-term item under "*"
-		is first summed into a scratch buffer ("tmp") and multiplied in afterwards.
+		The one walk over a chain of items.  An item is the SUM of its terms, one launch each; items are chained with the + / *
+		algebra of kernels.py:146-157.  Yields (term, target, combine, diag_add) for the caller to launch: target is ``out``, or for a
+		multi-term item under "*" a scratch (allocated at the first such item) that the item is summed in and that is folded in,
+		``out *= scratch``, after its last term.  ``diag_add`` rides on the last launch -- on the fold if the last launch folds.
 		"""
-		launches = []
+		tmp, left = None, sum(len(it['terms']) for it in items)
 		for it in items:
 			comb = {"-": _lib.OUT_SET, "+": _lib.OUT_ADD, "*": _lib.OUT_MUL}[it['op']]
-			scratch = it['op'] == "*" and len(it['terms']) > 1
+			fold = it['op'] == "*" and len(it['terms']) > 1
+			if fold and tmp is None:
+				tmp = torch.empty_like(out)
 			for t_i, t in enumerate(it['terms']):
-				first = _lib.OUT_SET if scratch else comb
-				launches.append(dict(term=t, target="tmp" if scratch else "out", combine=first if t_i == 0 else _lib.OUT_ADD, fold=False))
-			if scratch:
-				launches[-1]['fold'] = True          # out *= tmp after this launch
-		return launches
+				left -= 1
+				first = _lib.OUT_SET if fold else comb
+				yield t, tmp if fold else out, first if t_i == 0 else _lib.OUT_ADD, diag_add if (left == 0 and not fold) else 0.0
+			if fold and out.dim() == 1:          # (a diagonal folds as one row, and carries no noise term)
+				_lib.combine(out.reshape(1, -1), tmp.reshape(1, -1), _lib.OUT_MUL)
+			elif fold:
+				_lib.combine(out, tmp, _lib.OUT_MUL, diag_add if left == 0 else 0.0)
 
 	def _kernel_into(self, a, b, out, kwargs=None, diag_add=0.0, lower_only=False):
 		"""
 		Device-side evaluation: a (n, d), b (q, d) and out (q, n) are tensors on this process's
 		GPU.  ``diag_add`` (s^2 of gauss_procc.py:151-163) is applied with the last launch.
 		"""
-		items = self._resolve(dict(kwargs) if kwargs else {})
-		return self._run_items(items, a, b, out, diag_add, lower_only)
+		return self._run_items(self._chain(kwargs), a, b, out, diag_add, lower_only)
 
-	def _run_items(self, items, a, b, out, diag_add=0.0, lower_only=False, first_is_set=True):
-		"""Evaluates a list of resolved items into ``out``.  The first one's operation is taken as "set" unless
-		``first_is_set`` is False (then ``out`` already holds a value the chain continues from)."""
-		if first_is_set and items and items[0]['op'] != "-":
-			items = [dict(items[0], op="-")] + list(items[1:])
-		launches = self._plan(items)
-		dmax = max(len(l['term']['inv_ls']) for l in launches)
+	def _run_items(self, items, a, b, out, diag_add=0.0, lower_only=False):
+		"""Evaluates a chain of items into ``out`` with the operations as they stand: a first one other than "set" continues from
+		the value ``out`` holds."""
+		dmax = max(len(t['inv_ls']) for it in items for t in it['terms'])
 		work = _lib.gram_workspace(a.shape[0], b.shape[0], dmax, out)          # one scratch for every launch
-		tmp = None
 		same = a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride())
-		for idx, l in enumerate(launches):
-			t = l['term']
-			last = idx == len(launches) - 1
-			if l['target'] == "tmp" and tmp is None:
-				tmp = torch.empty_like(out)
-			target = tmp if l['target'] == "tmp" else out
+		for t, target, comb, dd in self._launches(items, out, diag_add):
+			am, bm = a, b
 			if t['premap'] is not None:
 				am = self._premap(a, t['group'], t['premap'])
 				bm = am if same else self._premap(b, t['group'], t['premap'])
-				cols = None
-			else:
-				am, bm = a, b
-				cols = None if t['group'] == list(range(a.shape[1])) else _dev_const(t['group'], None, out.device, int32=True)
-			inv_ls = _dev_const(t['inv_ls'], out.dtype, out.device)
-			_lib.gram(t['kind'], am, bm, target, inv_ls, cols, t['kappa'], t['offset'], diag_add=diag_add if (last and not l['fold']) else 0.0,
-					  lower_only=lower_only, combine=l['combine'], work=work)
-			if l['fold']:       # out *= (sum of the item's terms), then the noise term if this was the last launch
-				_lib.combine(out, tmp, _lib.OUT_MUL, diag_add if last else 0.0)
+			cols, inv_ls = self._term_operands(t, a if t['premap'] is None else None, out.dtype, out.device)
+			_lib.gram(t['kind'], am, bm, target, inv_ls, cols, t['kappa'], t['offset'], diag_add=dd, lower_only=lower_only, combine=comb, work=work)
 		return out
+
+	def _combine_into(self, items, a, b, out, op, scratch=None):
+		"""out (op)= the value of the chain ``items``, op one of _lib.OUT_SET / OUT_ADD / OUT_MUL.  A single item adds straight into
+		``out`` and, if it is one term, multiplies straight into it (the combine of stpy_gram); anything else is evaluated into a
+		scratch like ``out`` and combined by one stpy_combine.  Returns the scratch (``scratch`` if given, else allocated when needed)
+		for the caller to pass to its next call."""
+		if op == _lib.OUT_SET:
+			self._run_items(self._chain(items=items), a, b, out)
+		elif len(items) == 1 and (op == _lib.OUT_ADD or len(items[0]['terms']) == 1):
+			self._run_items([dict(items[0], op="+" if op == _lib.OUT_ADD else "*")], a, b, out)
+		else:
+			if scratch is None:
+				scratch = torch.empty_like(out)
+			self._run_items(self._chain(items=items), a, b, scratch)
+			_lib.combine(out, scratch, op)
+		return scratch
+
+	def _mul_factors_into(self, items, i, a, b, M, scratch=None):
+		"""M *= everything item i is multiplied with (d K / d K_i, see ``_factors``); ``scratch`` as in ``_combine_into``."""
+		for fac in self._factors(items, i):
+			scratch = self._combine_into(fac, a, b, M, _lib.OUT_MUL, scratch)
+		return scratch
 
 	@staticmethod
 	def _premap(x, group, cov):
@@ -358,23 +390,10 @@ class KernelFunction:
 		return _lib.like_input(out, a)
 
 	def _diag_into(self, x, out, kwargs=None, items=None):
-		if items is None:
-			items = self._resolve(dict(kwargs) if kwargs else {})
-		elif items and items[0]['op'] != "-":
-			items = [dict(items[0], op="-")] + list(items[1:])
-		tmp = None
-		for l in self._plan(items):
-			t = l['term']
-			if l['target'] == "tmp" and tmp is None:
-				tmp = torch.empty_like(out)
-			target = tmp if l['target'] == "tmp" else out
+		for t, target, comb, _ in self._launches(self._chain(kwargs, items), out):
 			# (a mapped stationary kernel has k(x, x) = kappa whatever the map; only dot-product kernels read x)
-			group = t['group'] if t['premap'] is None else list(range(x.shape[1]))
-			cols = None if group == list(range(x.shape[1])) else _dev_const(group, None, out.device, int32=True)
-			inv_ls = _dev_const(t['inv_ls'], out.dtype, out.device)
-			_lib.gram_diag(t['kind'], x, target, inv_ls, cols, t['kappa'], t['offset'], l['combine'], d=None if t['premap'] is None else 0)
-			if l['fold']:
-				_lib.combine(out.reshape(1, -1), tmp.reshape(1, -1), _lib.OUT_MUL)
+			cols, inv_ls = self._term_operands(t, x if t['premap'] is None else None, out.dtype, out.device)
+			_lib.gram_diag(t['kind'], x, target, inv_ls, cols, t['kappa'], t['offset'], comb, d=None if t['premap'] is None else 0)
 		return out
 
 	def kernel_self_diag(self, x, **kwargs):
@@ -413,9 +432,7 @@ class KernelFunction:
 		(G[:, group] += G_z cov^T, one stpy_gemm_nt); the factors of a * item enter through the coefficients:
 		C o prod_{l != j} K_l, formed with stpy_gram's multiply combine.
 		"""
-		items = self._resolve(dict(kwargs) if kwargs else {})
-		if items and items[0]['op'] != "-":
-			items = [dict(items[0], op="-")] + list(items[1:])
+		items = self._chain(kwargs)
 		if H is not None:
 			for it in items:
 				if it['op'] == "*":
@@ -438,22 +455,16 @@ class KernelFunction:
 				C += (u.reshape(-1, 1) if u is not None else 1.0) * alpha.reshape(1, -1)[:, :n]
 			if Wt is not None:
 				C += (v.reshape(-1, 1) if v is not None else 1.0) * Wt[:m, :n]
+		tmp = None
 		for i, it in enumerate(items):
-			factors = self._factors(items, i) if has_mul else []
-			if factors:
-				Ci = C.clone()
-				for fac in factors:
-					if len(fac) == 1 and len(fac[0]['terms']) == 1:
-						self._run_items([dict(fac[0], op="*")], x, xt, Ci, first_is_set=False)
-						continue
-					tmp = torch.empty((m, n), dtype=G.dtype, device=dev)
-					self._run_items(fac, x, xt, tmp)
-					_lib.combine(Ci, tmp, _lib.OUT_MUL)
-				coef = dict(Wt=Ci)
-			elif has_mul:
-				coef = dict(Wt=C)
-			else:
+			if not has_mul:
 				coef = dict(alpha=alpha, u=u, Wt=Wt, v=v)
+			elif self._factors(items, i):
+				Ci = C.clone()
+				tmp = self._mul_factors_into(items, i, x, xt, Ci, tmp)
+				coef = dict(Wt=Ci)
+			else:
+				coef = dict(Wt=C)
 			for t in it['terms']:
 				self._term_grad(t, x, xt, coef, G, H)
 		return G
@@ -469,7 +480,7 @@ class KernelFunction:
 			p = zx.shape[1]
 			Gz = torch.empty((m, p), dtype=G.dtype, device=dev)
 			Hz = torch.empty((m, p, p), dtype=G.dtype, device=dev) if H is not None else None
-			_lib.gram_grad(t['kind'], zx, zt, Gz, _dev_const([1.0] * p, G.dtype, dev), None, t['kappa'], t['offset'], combine=_lib.OUT_SET, H=Hz, **coef)
+			_lib.gram_grad(t['kind'], zx, zt, Gz, self._term_operands(t, None, G.dtype, dev)[1], None, t['kappa'], t['offset'], combine=_lib.OUT_SET, H=Hz, **coef)
 			cov = t['premap'].to(device=dev, dtype=G.dtype).contiguous()            # (dg, p): G_z cov^T is the NT product of G_z and cov
 			Gx = torch.empty((m, cov.shape[0]), dtype=G.dtype, device=dev)
 			_lib.gemm_nt(Gz, cov, Gx)
@@ -479,17 +490,14 @@ class KernelFunction:
 				Hx = torch.einsum("ap,tpq,bq->tab", cov, Hz, cov)
 				H[:, gi.reshape(-1, 1), gi.reshape(1, -1)] += Hx
 			return
-		group = t['group']
-		cols = None if group == list(range(x.shape[1])) else _dev_const(group, None, dev, int32=True)
-		_lib.gram_grad(t['kind'], x, xt, G, _dev_const(t['inv_ls'], G.dtype, dev), cols, t['kappa'], t['offset'], combine=_lib.OUT_ADD, H=H, **coef)
+		cols, inv_ls = self._term_operands(t, x, G.dtype, dev)
+		_lib.gram_grad(t['kind'], x, xt, G, inv_ls, cols, t['kappa'], t['offset'], combine=_lib.OUT_ADD, H=H, **coef)
 
 	def _self_grad_into(self, xt, coef, G, kwargs=None):
 		"""G[t] += coef_t * grad_x k(x, x) at x = xt_t: zero for stationary terms (k(x, x) = kappa); for the dot-product terms
 		2 kappa phi'(s) inv_ls^2 x with s = |x * inv_ls|^2 (+ offset), the product rule over * items with the k(x, x) of the other
 		factors (stpy_gram_diag).  O(m D) elementwise work on (m, D) tensors."""
-		items = self._resolve(dict(kwargs) if kwargs else {})
-		if items and items[0]['op'] != "-":
-			items = [dict(items[0], op="-")] + list(items[1:])
+		items = self._chain(kwargs)
 		m = xt.shape[0]
 		for i, it in enumerate(items):
 			gi = None

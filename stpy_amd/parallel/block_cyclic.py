@@ -101,16 +101,7 @@ class HipLocalOps:
 
 	def gram(self, kernel_object, xa, xb, out, kwargs=None, add=False):
 		"""out[j, i] (+)= k(xb_j, xa_i); out may be a strided 2-D view.  ``add``: the value is added to what ``out`` holds."""
-		if add:
-			items = kernel_object._resolve(dict(kwargs) if kwargs else {})
-			if len(items) == 1:
-				kernel_object._run_items([dict(items[0], op="+")], xa, xb, out, first_is_set=False)
-				return
-			tmp = torch.empty_like(out)
-			kernel_object._run_items(items, xa, xb, tmp)
-			self.add_into(out, tmp)
-			return
-		kernel_object._kernel_into(xa, xb, out, kwargs)
+		kernel_object._combine_into(kernel_object._chain(kwargs), xa, xb, out, _lib.OUT_ADD if add else _lib.OUT_SET)
 
 	def add_into(self, out, src):
 		"""out += src on (strided) 2-D views."""

@@ -183,3 +183,40 @@ def test_bench_more_ranks_than_gpus_prints_one_json_error_line():
 	assert r.returncode != 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
 	out = json.loads(lines[0])
 	assert out["value"] is None and out["n_gpus"] == 2 and "GPUs" in out["error"]
+
+
+def _add_case_se():
+	from stpy_amd.kernels import KernelFunction as KF
+	return KF(kernel_name="squared_exponential", gamma=0.9, kappa=1.3, d=4)
+
+
+def _add_case_composite():
+	from stpy_amd.kernels import KernelFunction as KF
+	return _add_case_se() * KF(kernel_name="matern", gamma=1.4, nu=2.5, d=4) + KF(kernel_name="ard", ard_gamma=[0.6, 0.9, 1.2, 1.5], kappa=0.7, d=4)
+
+
+@pytest.mark.parametrize("make", [_add_case_se, _add_case_composite], ids=["se_direct_add", "se*matern52+ard_through_scratch"])
+def test_local_gram_add_into_a_column_window(gpu_device, make):
+	"""HipLocalOps.gram(add=True), the S += k(xtest, x_K) of the distributed solve, on a column window of a wider matrix: one item
+	adds straight into the window with stpy_gram's add combine, a composite kernel goes through a scratch and one stpy_combine.
+	Against out0 + K with K from _kernel_into and the addition torch's.  Bound: each path rounds the sum at most twice (a fused
+	multiply-add in the epilogue included) and every value is positive, so |diff| <= 4 * 2^-52 * (|out0| + |K|) entry by entry."""
+	from stpy_amd.parallel.block_cyclic import HipLocalOps
+	q, n, d, c0 = 50, 70, 4, 20
+	rng = np.random.RandomState(5)
+	xa = torch.from_numpy(rng.uniform(-1, 1, size=(n, d))).cuda()
+	xb = torch.from_numpy(rng.uniform(-1, 1, size=(q, d))).cuda()
+	wide = torch.from_numpy(rng.uniform(0.5, 2.0, size=(q, n + 30))).cuda()
+	wide0 = wide.clone()
+	out = wide[:, c0:c0 + n]
+	kernel = make()
+	K = torch.empty((q, n), dtype=torch.float64, device=xa.device)
+	kernel._kernel_into(xa, xb, K)
+	assert float(K.min()) > 0
+	HipLocalOps().gram(kernel, xa, xb, out, add=True)
+	out0 = wide0[:, c0:c0 + n]
+	diff = (out - (out0 + K)).abs()
+	bound = 4 * 2.0 ** -52 * (out0.abs() + K.abs())
+	print("largest |diff| / bound: %.3g" % float((diff / bound).max()))
+	assert bool((diff <= bound).all())
+	assert torch.equal(wide[:, :c0], wide0[:, :c0]) and torch.equal(wide[:, c0 + n:], wide0[:, c0 + n:])          # nothing outside the window
