@@ -10,7 +10,8 @@
  *
  * Conventions
  *   - every data pointer is a DEVICE pointer into caller-owned memory (PyTorch-ROCm storage in the
- *     shipped host code); matrices are row-major with an explicit leading dimension in ELEMENTS;
+ *     shipped host code), with ONE exception, the index list `del_host` of stpy_potrf_delete (see there);
+ *     matrices are row-major with an explicit leading dimension in ELEMENTS;
  *   - dtype: 0 = float64, 1 = float32 (all operands of one call share it);
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it, nothing synchronises;
  *   - no allocation of data, no ownership transfer; workspaces are sized by the *_workspace_bytes queries and
@@ -177,6 +178,37 @@ int stpy_chol_update(int dtype, int64_t n, int64_t k, int sign,
                      void* L, int64_t ldl, void* winv, int64_t winv_elems,
                      void* W, int64_t ldw,
                      void* work, int64_t work_bytes, int32_t* info_dev, void* stream);
+
+/*
+ * Row deletion: the factor of K[R,R] + s^2 I from the resident factor of K + s^2 I, R the indices that are kept
+ * (GaussianProcess.remove_data_point(iterative=True); the reference can only refit).  n1 = n0 - k, n0p / n1p = n0 / n1 rounded up to a
+ * multiple of 128.  With S the deleted indices, L[R,R] is lower triangular (R increases) and
+ *     K[R,R] + s^2 I = L[R,R] L[R,R]^T + U U^T,   U = L[R,S]   (n1 x k),
+ * a rank-k POSITIVE update of the compacted triangle: the rotations of stpy_chol_update with sign = +1, no downdate, no pivot that can
+ * fail on finite data.  Rows of U above the first deleted index are zero, so the block columns left of 128 * floor(S[0] / 128) are
+ * copied and not rotated; deleting the last rows costs the copy alone, deleting row 0 one pass over L per 32 deleted rows: O(n^2 k)
+ * against the O(n^3) of a refit.
+ *   del_host: k strictly increasing indices in [0, n0).  This is the ONE HOST pointer of the ABI: the indices decide which device
+ *             addresses the gather reads, so they are validated on the host, before any HIP call -- a bad index is refused (-15) and can
+ *             never become an out-of-bounds device read, which a device-resident list could not promise without a round trip.  They
+ *             reach the head of `work` as kernel arguments (256 per launch on `stream`): the array has been read when the call
+ *             returns and may be freed at once, and the call waits for nothing, like every other entry point.
+ *   on entry: A (order n0p, lda >= n0p) holds a factor in the tile-padded layout stpy_potrf / stpy_potrf_append leave.
+ *   on exit:  B[0:n1p, 0:n1p] (ldb >= n1p) and winv blocks [0, n1p/128) are as stpy_potrf would leave them for the padded K[R,R] + s^2 I:
+ *             lower triangle, diagonal tiles whole with zeros above the diagonal, identity on rows / columns [n1, n1p); tiles strictly
+ *             above the diagonal are not written.  A is not written.  *info_dev = 0, or the 1-based first column whose pivot is not
+ *             finite (non-finite input only).
+ * The compaction is out of place (a workgroup's destination rows are other workgroups' source rows): A and B must not overlap (-16).
+ * Every sum has a fixed order: bit-reproducible.
+ * Refused, before any HIP call: dtype (-1), n0 < 1 (-2), k < 0 or k >= n0 (-3), NULL del_host / A / B / winv / work / info_dev
+ * (-4 / -5 / -7 / -9 / -11 / -13), indices out of range, unsorted or repeated (-15), lda < n0p (-6), ldb < n1p (-8), overlapping A and B
+ * (-16), winv_elems below the need of order n1p (-21), work_bytes < the query (-20).  k == 0: returns 0, nothing is read or written.
+ */
+int64_t stpy_potrf_delete_workspace_bytes(int dtype, int64_t n0, int64_t k);
+int stpy_potrf_delete(int dtype, int64_t n0, int64_t k, const int32_t* del_host,
+                      const void* A, int64_t lda, void* B, int64_t ldb,
+                      void* winv, int64_t winv_elems, void* work, int64_t work_bytes,
+                      int32_t* info_dev, void* stream);
 
 /* B <- B L^-T for B: m x n row-major (rows = right-hand sides).  With B = K* (M x N) this is
  * V^T = (L^-1 K*^T)^T of the variance term, gauss_procc.py:378,392.  From 2048 rows on: recursive

@@ -41,6 +41,8 @@ SIGNATURES = {
 	"stpy_potrf_append": (_i32, [_i32, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
 	"stpy_chol_update_workspace_bytes": (_i64, [_i32, _i64, _i64]),
 	"stpy_chol_update": (_i32, [_i32, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+	"stpy_potrf_delete_workspace_bytes": (_i64, [_i32, _i64, _i64]),
+	"stpy_potrf_delete": (_i32, [_i32, _i64, _i64, _c.POINTER(_c.c_int32), _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
 	"stpy_trsm_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32]),
 	"stpy_trsm_right_lt": (_i32, [_i32, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp]),
 	"stpy_potri": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
@@ -288,6 +290,19 @@ def chol_update(L, winv, W, sign=1):
 	work = _work(max(int(load().stpy_chol_update_workspace_bytes(dtype_code(L.dtype), n, k)), 1), L)
 	info = torch.zeros((1,), dtype=torch.int32, device=L.device)
 	_launch("stpy_chol_update", dtype_code(L.dtype), n, k, int(sign), ptr(L), ld(L), ptr(winv), winv.numel(), ptr(W), ld(W), ptr(work), work.numel(), ptr(info))
+	return info
+
+
+def potrf_delete(A, n0, idx, B, winv):
+	"""The factor of order n0 in A without the rows / columns ``idx`` (strictly increasing ints in [0, n0)), compacted into the
+	different buffer B with its inverse diagonal blocks in winv (layout: stpy_potrf_delete in the header).  The indices travel as a
+	host array, which the library validates and has read when the call returns (it passes them on as kernel arguments).  Returns the unread status word, as potrf."""
+	k = len(idx)
+	dt = dtype_code(A.dtype)
+	host = (_c.c_int32 * max(k, 1))(*idx)
+	work = _work(max(int(load().stpy_potrf_delete_workspace_bytes(dt, n0, k)), 1), A)
+	info = torch.zeros((1,), dtype=torch.int32, device=A.device)
+	_launch("stpy_potrf_delete", dt, n0, k, host, ptr(A), ld(A), ptr(B), ld(B), ptr(winv), winv.numel(), ptr(work), work.numel(), ptr(info))
 	return info
 
 

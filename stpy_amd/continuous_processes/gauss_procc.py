@@ -30,6 +30,7 @@ Differences a caller can observe, all deliberate:
 """
 import numpy as np
 import math
+import operator
 
 import torch
 
@@ -142,6 +143,38 @@ def _multistart_maximize(evaluate, starts, bounds, dev, dtype, final=None):
 	return res.x.reshape(S, d), vals.double().cpu().numpy(), count[0]
 
 
+def normalize_remove_index(index, n):
+	"""The rows ``remove_data_point`` is asked to drop from n points, as a sorted list of distinct ints in [0, n).  ``index``: an int, a
+	sequence of ints or a 1-D integer tensor / array; negative values count from the end.  IndexError for a value outside [-n, n),
+	ValueError for a repeated row (after the negative ones are resolved), TypeError for anything that is not an integer."""
+	if torch.is_tensor(index) or isinstance(index, np.ndarray):
+		if index.ndim > 1:
+			raise ValueError("remove_data_point: index must be an int or one-dimensional, got shape %s" % (tuple(index.shape),))
+		if torch.is_tensor(index) and (index.dtype.is_floating_point or index.dtype.is_complex or index.dtype == torch.bool):
+			raise TypeError("remove_data_point: index tensor of dtype %s (integers expected)" % index.dtype)
+		vals = index.reshape(-1).tolist()
+	elif isinstance(index, (list, tuple, range)):
+		vals = list(index)
+	else:
+		vals = [index]
+	out = []
+	for v in vals:
+		if isinstance(v, bool):
+			raise TypeError("remove_data_point: index %r is not an integer" % (v,))
+		try:
+			v = operator.index(v)
+		except TypeError:
+			raise TypeError("remove_data_point: index %r is not an integer" % (v,))
+		if v < -n or v >= n:
+			raise IndexError("remove_data_point: index %d is out of range for %d points" % (v, n))
+		out.append(v + n if v < 0 else v)
+	out.sort()
+	for a, b in zip(out, out[1:]):
+		if a == b:
+			raise ValueError("remove_data_point: row %d is listed more than once" % a)
+	return out
+
+
 class ResidentFactor:
 	"""The Cholesky factor of one (data, hyper-parameters) pair on the device, and what is derived from it at most once.  An estimator
 	holds it in ``_factor`` and drops all of it with ``_factor = None``.
@@ -214,6 +247,8 @@ class GaussianProcess(Estimator):
 		self.max_size = 10000               # gauss_procc.py:55: prediction chunk
 		self.clamp_variance = False         # the reference takes sqrt of the raw difference (:394-395)
 		self.nb = 0                         # outer panel width for potrf/trsm (0 = library default)
+		self.delete_max_rank = 128          # remove_data_point(iterative=True): more rows than this are refitted (each costs a rotation pass)
+		self.remove_path = None             # which route the last remove_data_point took: "update" or "refit"
 		if kernel is not None:
 			self.kernel_object = kernel
 			self.kernel = kernel.kernel
@@ -268,6 +303,45 @@ class GaussianProcess(Estimator):
 		self.fit_gp(self.x, self.y, Sigma=self._Sigma)
 
 	add_data = add_data_point
+
+	def remove_data_point(self, index, iterative=False):
+		"""Forget observations: ``index`` names rows of x / y (an int, a sequence of ints or a 1-D integer tensor; negative values count from
+		the end).  The default mirrors ``add_data_point``: slice the data and refit; a resident explicit Sigma is kept as Sigma[R][:, R]
+		when it is diagonal (the only form add_data_point builds), anything else is refused so that the caller refits explicitly.
+		``iterative=True`` deletes the rows from the resident factor instead (stpy_potrf_delete: a gather and, per 32 rows, one pass over
+		the part of L below the first deleted row) whenever that is the same mathematics -- the conditions of the append, and at most
+		``delete_max_rank`` rows -- and refits otherwise.  ``self.remove_path`` tells which ran ("update" / "refit").
+		IndexError: a row out of range; ValueError: a repeated row, every row, an unfitted or empty GP.  A refused call changes nothing."""
+		if not self.fitted or self.x is None or self.n == 0 or self._factor is None:
+			raise ValueError("remove_data_point: the GP holds no fitted data")
+		idx = normalize_remove_index(index, self.n)
+		if len(idx) == 0:
+			return
+		if len(idx) >= self.n:
+			raise ValueError("remove_data_point: cannot remove all %d points" % self.n)
+		Sigma = self._Sigma
+		if Sigma is not None:
+			Sigma = torch.as_tensor(Sigma)
+			if Sigma.dim() != 2 or Sigma.shape[0] != self.n or Sigma.shape[1] != self.n or not torch.equal(Sigma, torch.diag(torch.diagonal(Sigma))):
+				raise ValueError("remove_data_point: the explicit Sigma is not diagonal; slice the data and call fit_gp with the Sigma of the kept rows")
+		mask = torch.ones((self.n,), dtype=torch.bool)
+		mask[idx] = False
+		keep = mask.nonzero().reshape(-1)
+		n0 = self.n
+		if iterative and 1 <= len(idx) <= self.delete_max_rank and self._can_append(self.x, None):
+			if self._delete(idx, keep):
+				self.remove_path = "update"
+				return
+		x, y = self.x, self.y
+		if self.n == n0:                  # (else _delete has sliced them already: its factor was not good, or the hand-off of a solve gave up)
+			x, y = x[keep.to(x.device)], y[keep.to(y.device)]
+			if Sigma is not None:
+				ks = keep.to(Sigma.device)
+				Sigma = Sigma[ks][:, ks]
+		self.fit_gp(x, y, Sigma=Sigma)
+		self.remove_path = "refit"
+
+	remove_data = remove_data_point
 
 	def fit(self, x=None, y=None):
 		"""gauss_procc.py:113-117."""
@@ -423,6 +497,41 @@ class GaussianProcess(Estimator):
 		self._check_info(info)
 		_lib.check_async("add_data_point: stpy_potrf_append")
 		self._factor = ResidentFactor(buf[:n1p, :n1p], winv, n1, z=z, key=key, buf=buf)
+		self.fitted = True
+		return True
+
+	def _delete(self, idx, keep):
+		"""Drop the rows ``idx`` (sorted; ``keep``: the others, a long tensor) from the resident factor.  The compaction is out of place: the
+		new factor goes into a fresh buffer of the SAME capacity as the one it replaces, so that later appends stay in place.  Returns
+		False when the caller has to refit: before anything changed if that allocation fails, with x / y already sliced if the status
+		word or the solves' hand-off word is set."""
+		dtype, dev = self._xd.dtype, self._xd.device
+		old = self._factor
+		n0, n1 = self.n, self.n - len(idx)
+		n1p = _tile_pad(n1)
+		cap = (old.L if old.buf is None else old.buf).shape[0]
+		try:
+			nbuf = torch.zeros((cap, cap), dtype=dtype, device=dev)
+			nwinv = torch.empty((_lib.potrf_winv_elems(cap),), dtype=dtype, device=dev)
+		except RuntimeError:
+			nbuf = nwinv = None
+			return False
+		info = _lib.potrf_delete(old.L, n0, idx, nbuf, nwinv)
+		kd = keep.to(dev)
+		self.x, self.y, self.n = self.x[keep.to(self.x.device)], self.y[keep.to(self.y.device)], n1
+		self._xd, self._yd = self._xd[kd], self._yd[kd]
+		self.fitted = False
+		self._factor = None
+		F = ResidentFactor(nbuf[:n1p, :n1p], nwinv, n1, key=old.key, buf=nbuf)
+		F.solve(self._yd)                                                  # A = K^-1 y is part of the fitted state: two vector solves
+		ok = int(info.item()) == 0
+		try:
+			_lib.check_async("remove_data_point: stpy_trsv")
+		except _lib.StpyHipError:
+			ok = False
+		if not ok:
+			return False
+		self._factor = F
 		self.fitted = True
 		return True
 

@@ -14,7 +14,15 @@
 // access is a run of consecutive addresses, its kc entries of W stay in registers; the table of the 64 columns in flight sits
 // in LDS and is read with wave-uniform addresses).  At most CU_KC columns of W ride along in one pass over L; a wider W is cut into chunks, each a complete
 // update of its own.  One last launch rebuilds every inverse diagonal tile.  Every sum has a fixed order: bit-reproducible.
+//
+// Row deletion (stpy_potrf_delete, GaussianProcess.remove_data_point(iterative=True)) is the same update in disguise.  With S the deleted
+// and R the kept indices (both increasing), K[R,R] + s^2 I = L[R,:] L[R,:]^T = L[R,R] L[R,R]^T + U U^T, U = L[R,S]: L[R,R] is lower
+// triangular because R is sorted, so the new factor is a rank-k POSITIVE update of the compacted triangle -- no downdate, no pivot that can
+// fail on finite data.  A few small launches gather out of place (the indices, the index map R, the compacted triangle in the tile-padded layout
+// stpy_potrf leaves, U), then the passes above run on (B, U) from the block column of the first deleted index: rows of U above it are
+// zero, so the block columns to its left are copied and never rotated.
 #include <atomic>
+#include <limits.h>
 
 #include "common.h"
 
@@ -216,11 +224,11 @@ void cholupdate_trtri_kernel(const T* __restrict__ L, int64_t ldl, int64_t n, T*
 int64_t chol_update_workspace_bytes(size_t esz) { return (int64_t)IB * CU_KC * 3 * (int64_t)esz; }
 
 template <typename T, int KC>
-static int chol_update_pass(int64_t n, int kc, T sgn, T* L, int64_t ldl, T* Wc, int64_t ldw, T* tab, int32_t* info, hipStream_t st)
+static int chol_update_pass(int64_t n, int kc, T sgn, T* L, int64_t ldl, T* Wc, int64_t ldw, T* tab, int32_t* info, hipStream_t st, int64_t c_first)
 {
 	int rc;
 	const int lds = (int)cu_diag_lds(sizeof(T));
-	for (int64_t c0 = 0; c0 < n; c0 += IB) {
+	for (int64_t c0 = c_first; c0 < n; c0 += IB) {
 		hipLaunchKernelGGL((cholupdate_diag_kernel<T, KC>), dim3(1), dim3(IB), lds, st, L, ldl, (const T*)Wc, ldw, n, c0, kc, sgn, tab, info);
 		if ((rc = check_launch("chol_update (diagonal block)"))) return rc;
 		const int64_t below = n - c0 - IB;
@@ -233,8 +241,11 @@ static int chol_update_pass(int64_t n, int kc, T sgn, T* L, int64_t ldl, T* Wc, 
 	return 0;
 }
 
+// c_first: the first block column the passes visit (a multiple of 128; the rows of W above it are zero, so the block columns to its left
+// would see identity rotations).  k == 0: no pass, only the status word and the inverse diagonal tiles.
 template <typename T>
-int chol_update(int64_t n, int64_t k, int sign, T* L, int64_t ldl, T* winv, T* W, int64_t ldw, void* work, int32_t* info, hipStream_t st)
+int chol_update(int64_t n, int64_t k, int sign, T* L, int64_t ldl, T* winv, T* W, int64_t ldw, void* work, int32_t* info, hipStream_t st,
+                int64_t c_first = 0)
 {
 	static std::atomic<bool> attr_set[2];
 	const int which = sizeof(T) == 8 ? 0 : 1;
@@ -254,13 +265,166 @@ int chol_update(int64_t n, int64_t k, int sign, T* L, int64_t ldl, T* winv, T* W
 	// chunks of at most CU_KC columns of W, each a complete update of the factor the chunk before left
 	for (int64_t k0 = 0; k0 < k; k0 += CU_KC) {
 		const int kc = (int)(k - k0 < CU_KC ? k - k0 : CU_KC);
-		if (kc == 1) rc = chol_update_pass<T, 1>(n, kc, sgn, L, ldl, W + k0, ldw, tab, info, st);
-		else if (kc <= 8) rc = chol_update_pass<T, 8>(n, kc, sgn, L, ldl, W + k0, ldw, tab, info, st);
-		else rc = chol_update_pass<T, CU_KC>(n, kc, sgn, L, ldl, W + k0, ldw, tab, info, st);
+		if (kc == 1) rc = chol_update_pass<T, 1>(n, kc, sgn, L, ldl, W + k0, ldw, tab, info, st, c_first);
+		else if (kc <= 8) rc = chol_update_pass<T, 8>(n, kc, sgn, L, ldl, W + k0, ldw, tab, info, st, c_first);
+		else rc = chol_update_pass<T, CU_KC>(n, kc, sgn, L, ldl, W + k0, ldw, tab, info, st, c_first);
 		if (rc) return rc;
 	}
 	hipLaunchKernelGGL((cholupdate_trtri_kernel<T>), dim3((unsigned)((n + IB - 1) / IB)), dim3(IB), lds_tri, st, (const T*)L, ldl, n, winv);
 	return check_launch("chol_update (inverse diagonal tiles)");
+}
+
+// ------------------------------------------------------------------------------------------
+// Row deletion, step 0: the (host-validated) indices into the head of the workspace, PD_STAGE of them per launch, passed by value.
+// ------------------------------------------------------------------------------------------
+constexpr int PD_STAGE = 256;
+struct PdStage { int32_t v[PD_STAGE]; };
+
+__global__ __launch_bounds__(PD_STAGE)
+void potrf_delete_stage_kernel(PdStage stage, int cnt, int32_t* __restrict__ del)
+{
+	if ((int)threadIdx.x < cnt) del[threadIdx.x] = stage.v[threadIdx.x];
+}
+
+// ------------------------------------------------------------------------------------------
+// Row deletion, step 1: the index map.  rmap[i'] = R[i'] = i' + #{r : del[r] - r <= i'} for i' < n1 (del[r] - r does not decrease: a binary
+// search), 0 on the padding [n1, n1p).
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void potrf_delete_map_kernel(const int32_t* __restrict__ del, int k, int32_t* __restrict__ rmap, int64_t n1, int64_t n1p)
+{
+	const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n1p) return;
+	int lo = 0, hi = k;
+	while (lo < hi) {
+		const int mid = (lo + hi) >> 1;
+		if ((int64_t)del[mid] - mid <= i) lo = mid + 1;
+		else hi = mid;
+	}
+	rmap[i] = i < n1 ? (int32_t)(i + lo) : 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Step 2: B[i', j'] = A[R[i'], R[j']] on the lower tiles, in the layout stpy_potrf leaves at order n1p: diagonal tiles whole with zeros
+// above the diagonal, rows / columns [n1, n1p) of the identity; tiles strictly above the diagonal are not written.  HBM-bound, the
+// layout rules of gram.hip: lanes run along j', each owns 16 bytes of a row (2 / 4 adjacent columns: one store, 1 KiB per wave and row),
+// a workgroup takes PD_ROWS rows of one strip of 64 such lanes, its four waves alternating rows.  The source column R[j'] = j' + shift(j')
+// has a shift that does not decrease and is at most k, so a wave's reads are runs of consecutive addresses broken at most k times; a
+// lane's column indices are loaded once, the row index is wave-uniform.  vec: B and ldb are 16-byte aligned (else element stores).
+// ------------------------------------------------------------------------------------------
+constexpr int PD_ROWS = 32;
+
+template <typename T>
+__global__ __launch_bounds__(256)
+void potrf_delete_gather_kernel(const T* __restrict__ A, int64_t lda, T* __restrict__ B, int64_t ldb, const int32_t* __restrict__ rmap,
+                                int64_t n1, int64_t n1p, int vec)
+{
+	constexpr int V = 16 / (int)sizeof(T);
+	typedef T vT __attribute__((ext_vector_type(V)));
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int64_t i0 = (int64_t)blockIdx.y * PD_ROWS;
+	const int64_t j0 = ((int64_t)blockIdx.x * 64 + lane) * V;          // (a multiple of V: the V columns share one 128-tile)
+	if (j0 >= n1p) return;
+	const int64_t tj = j0 / IB;
+	if (tj > (i0 + PD_ROWS - 1) / IB) return;
+	int32_t src[V];
+#pragma unroll
+	for (int q = 0; q < V; ++q) src[q] = j0 + q < n1 ? rmap[j0 + q] : 0;
+#pragma unroll
+	for (int t = 0; t < PD_ROWS / 4; ++t) {
+		const int64_t i = i0 + wave + 4 * t;
+		if (i >= n1p || tj > i / IB) continue;
+		T v[V];
+		if (i < n1) {
+			const T* Ar = A + (int64_t)rmap[i] * lda;
+#pragma unroll
+			for (int q = 0; q < V; ++q) v[q] = j0 + q <= i ? Ar[src[q]] : T(0);
+		} else {
+#pragma unroll
+			for (int q = 0; q < V; ++q) v[q] = j0 + q == i ? T(1) : T(0);
+		}
+		T* Bi = B + i * ldb + j0;
+		if (vec) {
+			vT o;
+#pragma unroll
+			for (int q = 0; q < V; ++q) o[q] = v[q];
+			*(vT*)Bi = o;
+		} else {
+#pragma unroll
+			for (int q = 0; q < V; ++q) Bi[q] = v[q];
+		}
+	}
+}
+
+// ------------------------------------------------------------------------------------------
+// Step 3: U[i', r] = A[R[i'], del[r]] where del[r] < R[i'] (the part of the deleted columns left of the diagonal), else 0; n1p rows of k
+// contiguous elements, rows [n1, n1p) zero.  Lanes run along r, then i': the STORES are consecutive; the reads are not -- a lane's
+// source is one element of row R[i'], k scattered elements per row and a stride of lda between rows (for k = 1 a column walk), n1 k
+// elements in all, a 1 / n1 share of what the gather moves and nothing beside a rotation pass.
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256)
+void potrf_delete_u_kernel(const T* __restrict__ A, int64_t lda, const int32_t* __restrict__ del, const int32_t* __restrict__ rmap,
+                           T* __restrict__ U, int64_t n1, int64_t total, int k)
+{
+	for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+		const int64_t i = idx / k;
+		const int r = (int)(idx - i * k);
+		T v = T(0);
+		if (i < n1) {
+			const int32_t ri = rmap[i], s = del[r];
+			if (s < ri) v = A[(int64_t)ri * lda + s];
+		}
+		U[idx] = v;
+	}
+}
+
+static inline int64_t pd_pad(int64_t n) { return (n + IB - 1) / IB * IB; }
+static inline int64_t pd_round16(int64_t b) { return (b + 15) / 16 * 16; }
+// workspace of stpy_potrf_delete: [del: k int32][rmap: pad(n0) int32][rotation table][U: pad(n0) x k], each part 16-byte aligned.  Sized by
+// pad(n0), not pad(n0 - k), so that the query does not shrink when k grows.
+static inline int64_t pd_off_map(int64_t k) { return pd_round16(4 * k); }
+static inline int64_t pd_off_tab(int64_t n0, int64_t k) { return pd_off_map(k) + 4 * pd_pad(n0); }
+static inline int64_t pd_off_u(size_t esz, int64_t n0, int64_t k) { return pd_off_tab(n0, k) + pd_round16(chol_update_workspace_bytes(esz)); }
+int64_t potrf_delete_workspace_bytes(size_t esz, int64_t n0, int64_t k) { return pd_off_u(esz, n0, k) + pd_round16(pd_pad(n0) * k * (int64_t)esz); }
+
+template <typename T>
+int potrf_delete(int64_t n0, int64_t k, const int32_t* del_host, const T* A, int64_t lda, T* B, int64_t ldb, T* winv, void* work, int32_t* info,
+                 hipStream_t st)
+{
+	const int64_t n1 = n0 - k, n1p = pd_pad(n1);
+	char* w = (char*)work;
+	int32_t* del = (int32_t*)w;
+	int32_t* rmap = (int32_t*)(w + pd_off_map(k));
+	void* tab = w + pd_off_tab(n0, k);
+	T* U = (T*)(w + pd_off_u(sizeof(T), n0, k));
+	int rc;
+	// the indices travel as kernel ARGUMENTS, PD_STAGE at a time: a launch copies its arguments, so del_host has been read when this
+	// returns and nothing waits for the stream (a copy from pageable host memory would make the runtime drain the stream first)
+	for (int64_t r0 = 0; r0 < k; r0 += PD_STAGE) {
+		PdStage stage;
+		const int cnt = (int)(k - r0 < PD_STAGE ? k - r0 : PD_STAGE);
+		for (int q = 0; q < PD_STAGE; ++q) stage.v[q] = q < cnt ? del_host[r0 + q] : 0;
+		hipLaunchKernelGGL(potrf_delete_stage_kernel, dim3(1), dim3(PD_STAGE), 0, st, stage, cnt, del + r0);
+		if ((rc = check_launch("potrf_delete (indices)"))) return rc;
+	}
+	hipLaunchKernelGGL(potrf_delete_map_kernel, dim3((unsigned)((n1p + 255) / 256)), dim3(256), 0, st, (const int32_t*)del, (int)k, rmap, n1, n1p);
+	if ((rc = check_launch("potrf_delete (index map)"))) return rc;
+	constexpr int V = 16 / (int)sizeof(T);
+	const int vec = ((uintptr_t)B % 16 == 0 && ldb % V == 0) ? 1 : 0;
+	hipLaunchKernelGGL((potrf_delete_gather_kernel<T>), dim3((unsigned)((n1p + 64 * V - 1) / (64 * V)), (unsigned)((n1p + PD_ROWS - 1) / PD_ROWS)), dim3(256), 0, st,
+	                   A, lda, B, ldb, (const int32_t*)rmap, n1, n1p, vec);
+	if ((rc = check_launch("potrf_delete (gather)"))) return rc;
+	// U is zero above the first deleted row: all of it when the deleted rows are the last ones -- then the compacted triangle IS the factor
+	const bool rotate = del_host[0] < n1;
+	if (rotate) {
+		const int64_t total = n1p * k;
+		const int64_t blocks = (total + 255) / 256;
+		hipLaunchKernelGGL((potrf_delete_u_kernel<T>), dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, A, lda, (const int32_t*)del,
+		                   (const int32_t*)rmap, U, n1, total, (int)k);
+		if ((rc = check_launch("potrf_delete (deleted columns)"))) return rc;
+	}
+	return chol_update<T>(n1, rotate ? k : 0, 1, B, ldb, winv, U, k, tab, info, st, rotate ? (del_host[0] / IB) * IB : 0);
 }
 
 }  // namespace stpy
@@ -304,6 +468,58 @@ int stpy_chol_update(int dtype, int64_t n, int64_t k, int sign, void* L, int64_t
 	if (dtype == STPY_F64)
 		return chol_update<double>(n, k, sign, (double*)L, ldl, (double*)winv, (double*)W, ldw, work, info_dev, st);
 	return chol_update<float>(n, k, sign, (float*)L, ldl, (float*)winv, (float*)W, ldw, work, info_dev, st);
+}
+
+int64_t stpy_potrf_delete_workspace_bytes(int dtype, int64_t n0, int64_t k)
+{
+	if (n0 <= 0 || k <= 0) return 0;
+	return potrf_delete_workspace_bytes(dtype == STPY_F32 ? 4 : 8, n0, k);
+}
+
+int stpy_potrf_delete(int dtype, int64_t n0, int64_t k, const int32_t* del_host, const void* A, int64_t lda, void* B, int64_t ldb,
+                      void* winv, int64_t winv_elems, void* work, int64_t work_bytes, int32_t* info_dev, void* stream)
+{
+	if (k == 0) return 0;          // nothing to delete: nothing is read or written
+	if (dtype != STPY_F64 && dtype != STPY_F32) { set_error("stpy_potrf_delete: unknown dtype %d (0 = float64, 1 = float32)", dtype); return -1; }
+	if (n0 < 1 || n0 > INT32_MAX) { set_error("stpy_potrf_delete: n0=%lld (1 .. 2^31 - 1)", (long long)n0); return -2; }
+	if (k < 0 || k >= n0) { set_error("stpy_potrf_delete: k=%lld rows of n0=%lld (0 <= k < n0)", (long long)k, (long long)n0); return -3; }
+	if (!del_host) { set_error("stpy_potrf_delete: null pointer del_host"); return -4; }
+	if (!A) { set_error("stpy_potrf_delete: null pointer A"); return -5; }
+	if (!B) { set_error("stpy_potrf_delete: null pointer B"); return -7; }
+	if (!winv) { set_error("stpy_potrf_delete: null pointer winv"); return -9; }
+	if (!work) { set_error("stpy_potrf_delete: null pointer work"); return -11; }
+	if (!info_dev) { set_error("stpy_potrf_delete: null pointer info_dev"); return -13; }
+	for (int64_t r = 0; r < k; ++r) {
+		if (del_host[r] < 0 || del_host[r] >= n0) {
+			set_error("stpy_potrf_delete: del_host[%lld]=%d outside [0, n0=%lld)", (long long)r, (int)del_host[r], (long long)n0);
+			return -15;
+		}
+		if (r > 0 && del_host[r] <= del_host[r - 1]) {
+			set_error("stpy_potrf_delete: del_host[%lld]=%d after %d: the indices must increase strictly", (long long)r, (int)del_host[r], (int)del_host[r - 1]);
+			return -15;
+		}
+	}
+	const int64_t n0p = pd_pad(n0), n1p = pd_pad(n0 - k);
+	if (lda < n0p) { set_error("stpy_potrf_delete: lda=%lld below the padded old order %lld", (long long)lda, (long long)n0p); return -6; }
+	if (ldb < n1p) { set_error("stpy_potrf_delete: ldb=%lld below the padded new order %lld", (long long)ldb, (long long)n1p); return -8; }
+	const int64_t esz = dtype == STPY_F32 ? 4 : 8;
+	const uintptr_t a0 = (uintptr_t)A, a1 = a0 + (uintptr_t)(((n0p - 1) * lda + n0p) * esz);
+	const uintptr_t b0 = (uintptr_t)B, b1 = b0 + (uintptr_t)(((n1p - 1) * ldb + n1p) * esz);
+	if (a0 < b1 && b0 < a1) { set_error("stpy_potrf_delete: A and B overlap (the compaction is out of place)"); return -16; }
+	const int64_t winv_need = (n1p / IB) * (int64_t)IB * IB;
+	if (winv_elems < winv_need) {
+		set_error("stpy_potrf_delete: winv holds %lld elements, %lld needed (stpy_potrf_winv_elems of the new order)", (long long)winv_elems, (long long)winv_need);
+		return -21;
+	}
+	const int64_t work_need = stpy_potrf_delete_workspace_bytes(dtype, n0, k);
+	if (work_bytes < work_need) {
+		set_error("stpy_potrf_delete: workspace of %lld bytes, %lld needed (stpy_potrf_delete_workspace_bytes)", (long long)work_bytes, (long long)work_need);
+		return -20;
+	}
+	hipStream_t st = (hipStream_t)stream;
+	if (dtype == STPY_F64)
+		return potrf_delete<double>(n0, k, del_host, (const double*)A, lda, (double*)B, ldb, (double*)winv, work, info_dev, st);
+	return potrf_delete<float>(n0, k, del_host, (const float*)A, lda, (float*)B, ldb, (float*)winv, work, info_dev, st);
 }
 
 }  // extern "C"

@@ -502,6 +502,7 @@ void trsv_bwd_step(const T* __restrict__ L, int64_t ldl, const T* __restrict__ W
 // stpy_async_status): a timed-out solve also poisons its output with NaN, so the failure shows in every result derived from it
 // (TrsvSync, load_sc1 / store_sc1: common.h -- the multi-right-hand-side solve of append.hip shares them)
 int g_trsv_flow = 1;           // stpy_tune key 16: 0 = always the chain of step kernels
+constexpr unsigned TRSV_FAILED = 0x80000000u;          // flag in the published counter: the publishing workgroup's own wait gave up
 
 template <typename T, bool BACK>
 __global__ __launch_bounds__(256, 1)
@@ -545,14 +546,17 @@ void trsv_flow_kernel(const T* __restrict__ L, int64_t ldl, const T* __restrict_
 			// (a workgroup far behind the front sleeps longer between polls: a hundred workgroups hammering one word slow the
 			// publisher's own write-through stores down)
 			unsigned c = load_sc1(&sy->count);
-			for (int spin = 0; (int)c <= j && spin < 1000000; ++spin) {
+			for (int spin = 0; !(c & TRSV_FAILED) && (int)c <= j && spin < 1000000; ++spin) {
 				const int dist = k - (int)c;
 				if (dist > 8) __builtin_amdgcn_s_sleep(127); else if (dist > 2) __builtin_amdgcn_s_sleep(32); else __builtin_amdgcn_s_sleep(2);
 				c = load_sc1(&sy->count);
 			}
 			// give up rather than hang -- LOUDLY: the sticky error word (stpy_async_status) and, below, NaN in this block of the
-			// output, which every later block and every quantity derived from the solve inherits
-			if ((int)c <= j) { atomicExch(&sy->error, 1u); s_failed = 1; c = (unsigned)nblk; }
+			// output, which every later block and every quantity derived from the solve inherits.  A counter published by a workgroup
+			// that gave up carries TRSV_FAILED: whoever is still waiting then -- a block with a LOWER ticket included, whose own wait
+			// would have run out a moment later (the two blocks next to the front poll at the same rate) -- fails with it, instead of
+			// taking that counter for the hand-off it was waiting for and publishing numbers behind a block that never arrived
+			if ((c & TRSV_FAILED) || (int)c <= j) { atomicExch(&sy->error, 1u); s_failed = 1; c = (unsigned)nblk; }
 			s_ready = (int)c;
 		}
 		__syncthreads();
@@ -665,7 +669,7 @@ void trsv_flow_kernel(const T* __restrict__ L, int64_t ldl, const T* __restrict_
 #if STPY_LAB
 	if (k + 1 == fault_ticket) return;      // test hook (stpy_tune key 22 = ticket + 1; 0 = off): this block is never published -> its successor's wait must time out
 #endif
-	if (tid == 0) store_sc1(&sy->count, (unsigned)(k + 1));
+	if (tid == 0) store_sc1(&sy->count, (unsigned)(k + 1) | (s_failed ? TRSV_FAILED : 0u));
 }
 
 // sticky error word of the vector solves issued on `st`: waits for the stream, returns the word and clears it
