@@ -355,11 +355,14 @@ int stpy_gemm_nt_bc(int dtype, int64_t m, int64_t n, int64_t k, const void* A, i
 	if (!A || !B || !C) { set_error("stpy_gemm_nt_bc: null pointer"); return -5; }
 	if (k < 0 || lda < k || ldb < k || ldc < n) { set_error("stpy_gemm_nt_bc: leading dimensions"); return -6; }
 	if (pr <= 0 || pc <= 0 || myr < 0 || myr >= pr || myc < 0 || myc >= pc || i0 < 0 || j0 < 0) { set_error("stpy_gemm_nt_bc: bad process-grid arguments"); return -13; }
+	if (mode < 0 || mode > 2) { set_error("stpy_gemm_nt_bc: mode %d (0: C = A B^T, 1: C -= A B^T, 2: C += A B^T)", mode); return -11; }
+	if (mode == 2) mode = 5;          // (internal numbering, as stpy_gemm_nt)
+	if (nb_dist <= 0 || nb_dist % 128 != 0) { set_error("stpy_gemm_nt_bc: distribution block %d must be a positive multiple of 128", nb_dist); return -13; }
 	hipStream_t st = (hipStream_t)stream;
 	BlockCyclic bc{nb_dist, pr, pc, myr, myc, i0, j0};
 	// algorithmic flops: only the distribution blocks on or below the global diagonal are computed
 	double elems = (double)m * (double)n;
-	if (g_prof_on.load() && nb_dist >= 128 && nb_dist % 128 == 0) {
+	if (g_prof_on.load()) {
 		elems = 0;
 		for (int64_t bi = 0; bi * nb_dist < m; ++bi) {
 			const int64_t I = (bi + i0) * pr + myr, rows = std::min<int64_t>(nb_dist, m - bi * nb_dist);
