@@ -1,7 +1,8 @@
 /*
  * stpy_hip.h -- C ABI of libstpy_hip.so: the MI355X (gfx950) implementation of the dense
  * linear-algebra hot path of Mojusko/stpy (kernel Gram matrices, blocked Cholesky, triangular
- * solves, GP prediction epilogue, log-marginal reductions, random-Fourier-feature embed).
+ * solves, GP prediction epilogue, log-marginal reductions, random-Fourier-feature embed,
+ * pivoted partial Cholesky of an on-the-fly kernel matrix for Nystrom landmarks).
  *
  * The reference has no FFI of its own: the path sits behind Python methods that call torch CPU
  * ops.  Each entry point below replaces the torch/scipy call sequence cited next to it
@@ -388,6 +389,36 @@ int stpy_lml_batch(int kind, int dtype, const void* x, int64_t n, int64_t ldx, i
                    const int32_t* pidx, int np,
                    void* value, void* grad, int64_t ldg, int32_t* info,
                    void* work, int64_t work_bytes, void* stream);
+
+/*
+ * Greedy pivoted partial Cholesky of the kernel matrix K_il = kappa phi(|(x_i - x_l)[cols] o inv_ls|), columns generated on the fly: the landmark
+ * choice of NystromFeatures(approx="pivoted") (the reference's nystrom_fea.py has uniform / leverage sampling only).  K is never formed:
+ * O(n m) memory, O(n m^2) work.  kind, cols, inv_ls, kappa as for stpy_gram; SE and MATERN12 / 32 / 52 only.  Kernel values come from direct
+ * coordinate differences, as in stpy_lml_batch: kappa (d + 8) eps wherever the data lies, exactly kappa on coincident points.
+ *   start:   dres[i] = kappa for every i < n.
+ *   step j = 0 .. m-1:  p = argmax_i dres[i], ties to the LOWEST index; dres[p] <= tol * kappa or dres[p] <= 0 stops with rank r = j; otherwise
+ *            piv[j] = p,  Ft[j*ldf + i] = (K_ip - sum_{l<j} Ft[l*ldf + i] Ft[l*ldf + p]) / sqrt(dres[p]),  dres[i] -= Ft[j*ldf + i]^2,  dres[p] = 0 exactly.
+ *   on exit: *rank_dev = r; rows [r, m) of Ft are zero; piv[r:m) = -1; dres (n elements) is the residual diagonal diag(K - F F^T), exactly 0 on the
+ *            pivots, whose sum is the trace-norm error of the approximation; the pivots are pairwise distinct.
+ * Ft is m x n (ldf >= n): row j is column j of the factor F, the "row x K" operand stpy_syrk and stpy_gemm_nt take.  piv: device int32[m].
+ * m <= min(n, 8192).  The cap is the launch count of one call, not a memory budget: a step is one launch, and the values Ft[0:j, p] a step needs
+ * pass through LDS in chunks of 1024, so LDS sets no limit on m.
+ * One enqueue sequence on `stream` (m + 2 launches), no host synchronisation, no allocation: the stop is the device word *rank_dev, and the
+ * launches after it return on reading it.  No workgroup waits for another inside a launch (no spin-waits, no cooperative grid, no atomics):
+ * every workgroup owns a tile of points, reduces the per-tile (value, index) argmaxes of the previous launch in `work` -- all arrive at the same
+ * p --, streams its tile's rows of Ft with 16-byte loads per lane (when Ft is 16-byte aligned and ldf a multiple of 16 bytes; element-wise
+ * otherwise, same results) and writes its own argmax to the other half of `work`.  Every sum has a fixed order: two calls on the same input
+ * are bit-identical.  Step j reads j * n elements; a run of rank r reads esz * n * r (r - 1) / 2 bytes, a streaming read whose ceiling is HBM
+ * once Ft outgrows the Infinity Cache.
+ * Refused before any HIP call: kind (-1), dtype (-2), NULL x / inv_ls / Ft / dres / piv / rank_dev / work (-3), n < 0 or n >= 2^31 (-4), ldx < d (-5),
+ * d < 1 (-6), m < 1, m > n or m > 8192 (-10), tol negative or not finite (-11), ldf < n (-13), work not 8-byte aligned (-17), work_bytes below
+ * stpy_pchol_workspace_bytes(dtype, n, d, m) (-20).  n == 0: returns 0, nothing is read or written.
+ */
+int64_t stpy_pchol_workspace_bytes(int dtype, int64_t n, int d, int64_t m);
+int stpy_pchol(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+               double kappa, int64_t m, double tol,
+               void* Ft, int64_t ldf, void* dres, int32_t* piv, int32_t* rank_dev,
+               void* work, int64_t work_bytes, void* stream);
 
 /*
  * Input gradients of the GP posterior (gauss_procc.py:420-459 mean_gradient_hessian / gradient_mean_var and the

@@ -68,6 +68,8 @@ SIGNATURES = {
 	"stpy_lml_batch_max_n": (_i64, []),
 	"stpy_lml_batch_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_lml_batch": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _dbl, _dbl, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+	"stpy_pchol_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
+	"stpy_pchol": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _i64, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 	"stpy_gram_grad_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i32]),
 	"stpy_gram_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_trsm_ln_factor": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
@@ -437,6 +439,21 @@ def lml_batch(kind, x, y, inv_ls, noise, pidx, n_params, kappa, weight, cols=Non
 	_launch("stpy_lml_batch", kind, dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(y), B, ptr(inv_ls), ld(inv_ls), ptr(noise),
 			float(kappa), float(weight), ptr(pidx), int(n_params), ptr(value), ptr(grad), ldg, ptr(info), ptr(work), work.numel())
 	return value, grad, info, packed
+
+
+def pchol(kind, x, inv_ls, m, cols=None, kappa=1.0, tol=0.0, ldf=None):
+	"""Greedy pivoted partial Cholesky of the kernel matrix of the rows of x (stpy_pchol in the header), at most m steps.  Returns
+	(piv (m,) int32, Ft (m, n), dres (n,), rank (1,) int32), all on the device and unread: rows of Ft and entries of piv from the rank on
+	are 0 / -1.  ldf: row stride of Ft's storage (default n), of which Ft is the first n columns."""
+	n, d = x.shape[0], _ncols(x, cols)
+	Ft = torch.empty((m, n if ldf is None else int(ldf)), dtype=x.dtype, device=x.device)[:, :n]
+	dres = torch.empty((n,), dtype=x.dtype, device=x.device)
+	piv = torch.empty((m,), dtype=torch.int32, device=x.device)
+	rank = torch.empty((1,), dtype=torch.int32, device=x.device)
+	work = _work(load().stpy_pchol_workspace_bytes(dtype_code(x.dtype), n, d, m), x)
+	_launch("stpy_pchol", kind, dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), float(kappa), m, float(tol), ptr(Ft), ld(Ft),
+			ptr(dres), ptr(piv), ptr(rank), ptr(work), work.numel())
+	return piv, Ft, dres, rank
 
 
 def rff_embed(x, W, m, scale, bias=None, feat_scale=None, transposed=False, workspace=False):

@@ -602,3 +602,8 @@ int stpy_profile_read_union(int tagmask, double* busy_ms, double* total_flops, i
 }
 
 }  // extern "C"
+
+// stpy_pchol / stpy_pchol_workspace_bytes: kernels, launcher and argument checks are a file of their own (pchol.hip, which also compiles
+// alone for the resource-usage checks), compiled as part of THIS translation unit -- whatever builds the library from its list of
+// sources gets the entry points with api.hip, and the exported symbols stay exactly the header's.
+#include "pchol.hip"
