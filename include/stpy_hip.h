@@ -421,6 +421,57 @@ int stpy_pchol(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d
                void* work, int64_t work_bytes, void* stream);
 
 /*
+ * Kernel matrix times a block of vectors, the matrix never formed (IterativeGaussianProcess; the reference has no matrix-free route):
+ *   Yt[c*ldy + i] = sum_{j<q} kappa phi(|(a_i - b_j)[cols] o inv_ls|) Vt[c*ldv + j] + diag_add Vt[c*ldv + i],     c < t, i < n
+ * kind, cols, inv_ls, kappa as for stpy_pchol; SE and MATERN12 / 32 / 52 only.  Block vectors are stored TRANSPOSED, one right-hand side per row
+ * (Vt: t x q, Yt: t x n): the orientation KernelFunction._kernel_into writes and the "row x K" operand of stpy_gemm_nt.  Yt must not overlap Vt.
+ * Kernel values come from direct coordinate differences with the evaluator of stpy_pchol (the same bits): kappa (d + 8) eps wherever the data
+ * lies, exactly kappa on coincident points; with a == b the operator is bitwise symmetric and is the one a stpy_pchol factor was built from.
+ * diag_add != 0 needs q == n: the caller states that a and b are the same points.
+ * A workgroup owns 64 output points and walks j in a fixed order; on the 16x16x4 MFMA a lane evaluates the one kernel value its B operand
+ * wants, and up to 64 right-hand sides share an evaluation.  With too few output tiles to fill the chip the j range is cut into pieces whose
+ * partial sums pass through `work` and are added in piece order: no atomics, no spin-waits, no cooperative grid.  Two calls on the same input are
+ * bit-identical, and ldv / ldy do not change a bit.  One or two launches, no host synchronisation, no allocation.
+ * Refused before any HIP call: kind (-1), dtype (-2), NULL a / b / inv_ls / Vt / Yt (-3), n or q negative or >= 2^31 (-4), lda or ldb < d (-5),
+ * d < 1 (-6), t < 1 (-10), kappa or diag_add not finite (-11), diag_add != 0 with q != n (-12), ldv < q or ldy < n (-13), work not 8-byte aligned
+ * (-17), work NULL or work_bytes below stpy_kmv_workspace_bytes(dtype, n, q, d, t) (-20; the query does not decrease in n, q or t).
+ * n == 0: returns 0, nothing is read or written.  q == 0: Yt = 0.
+ */
+int64_t stpy_kmv_workspace_bytes(int dtype, int64_t n, int64_t q, int d, int64_t t);
+int stpy_kmv(int kind, int dtype,
+             const void* a, int64_t n, int64_t lda,
+             const void* b, int64_t q, int64_t ldb,
+             int d, const int32_t* cols, const void* inv_ls, double kappa, double diag_add,
+             const void* Vt, int64_t t, int64_t ldv,
+             void* Yt, int64_t ldy,
+             void* work, int64_t work_bytes, void* stream);
+
+/*
+ * Block preconditioned conjugate gradients on the operator of stpy_kmv: (K(x, x) + diag_add I) X_c = B_c for t independent columns, the rows of
+ * Bt / Xt (t x n).  Preconditioner M^-1 = I - G G^T with G (n x r) given as Gn (n x r, ldgn >= r) AND as its transpose Gt (r x n, ldgt >= n), so
+ * that both products are NT products on the library's MFMA contraction; with C = s^2 I + F^T F = L L^T and G = F L^-T this is s^2 times the
+ * Woodbury inverse of s^2 I + F F^T (F a stpy_pchol factor) -- a constant factor on M^-1 does not change the iterates.  r == 0: plain CG.
+ * One call enqueues exactly `iters` iterations (one stpy_kmv, two products, two vector kernels each): no host synchronisation, no allocation.  The
+ * state (R, P, Z, Q, the per-column scalars) lives in `work` and persists between calls: init != 0 starts from X = 0, init == 0 continues, and k
+ * calls of 10 iterations give the bits of one call of 10 k.  Dot products are accumulated in double in a fixed order, one workgroup per column.
+ * A column with |R_c| <= tol |B_c| (recurrence residual) is frozen: its X, R and its[c] never change again.  A zero column: X = 0, its = 0,
+ * relres = 0.  A column whose curvature <P_c, A P_c> (or <R_c, M^-1 R_c>) is not positive and finite is frozen with its[c] = -(iteration), X at
+ * the last good iterate.  Written after the last iteration of the call (elements of the matrix type): relres[c] = |R_c| / |B_c|, bx[c] = <B_c, X_c>;
+ * its[c]: device int32.
+ * Refused before any HIP call: as stpy_kmv (kind -1, dtype -2, NULL x / inv_ls / Bt / Xt / relres / bx / its -3, n -4, ldx < d -5, d < 1 -6, t < 1
+ * -10, kappa / diag_add -11), ldb or ldxt < n (-13), tol negative or not finite (-14), iters < 0 (-15), r < 0 (-16), r > 0 with NULL Gt / Gn (-3),
+ * ldgt < n or ldgn < r (-18), work not 16-byte aligned (-17), work NULL or below stpy_pcg_workspace_bytes(dtype, n, d, t, r) (-20).  n == 0: returns 0.
+ */
+int64_t stpy_pcg_workspace_bytes(int dtype, int64_t n, int d, int64_t t, int64_t r);
+int stpy_pcg(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+             double kappa, double diag_add,
+             const void* Gt, int64_t ldgt, const void* Gn, int64_t ldgn, int64_t r,
+             const void* Bt, int64_t ldb, void* Xt, int64_t ldxt, int64_t t,
+             double tol, int iters, int init,
+             void* relres, void* bx, int32_t* its,
+             void* work, int64_t work_bytes, void* stream);
+
+/*
  * Input gradients of the GP posterior (gauss_procc.py:420-459 mean_gradient_hessian / gradient_mean_var and the
  * autograd of mean_std through a test tensor with requires_grad; ucb_optimize, :918-963).  One kernel term k = kappa phi,
  * test points xt (m x ldt) against training points x (n x ldx), scaled differences e = (xt - x_i)[cols] * inv_ls:

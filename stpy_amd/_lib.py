@@ -70,6 +70,11 @@ SIGNATURES = {
 	"stpy_lml_batch": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _dbl, _dbl, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_pchol_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_pchol": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _i64, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+	"stpy_kmv_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i64]),
+	"stpy_kmv": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+	"stpy_pcg_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64, _i64]),
+	"stpy_pcg": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _dbl, _i32, _i32,
+						_vp, _vp, _vp, _vp, _i64, _vp]),
 	"stpy_gram_grad_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i32]),
 	"stpy_gram_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_trsm_ln_factor": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
@@ -454,6 +459,37 @@ def pchol(kind, x, inv_ls, m, cols=None, kappa=1.0, tol=0.0, ldf=None):
 	_launch("stpy_pchol", kind, dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), float(kappa), m, float(tol), ptr(Ft), ld(Ft),
 			ptr(dres), ptr(piv), ptr(rank), ptr(work), work.numel())
 	return piv, Ft, dres, rank
+
+
+def kmv_workspace(n, q, d, t, like):
+	"""Scratch of stpy_kmv (the partial sums of a cut j range); one buffer can serve several launches."""
+	return _work(load().stpy_kmv_workspace_bytes(dtype_code(like.dtype), n, q, d, t), like)
+
+
+def kmv(kind, a, b, Vt, Yt, inv_ls, cols=None, kappa=1.0, diag_add=0.0, work=None):
+	"""Yt[c, i] = sum_j k(a_i, b_j) Vt[c, j] + diag_add Vt[c, i], the kernel matrix never formed (stpy_kmv in the header).  Vt: (t, |b|),
+	Yt: (t, |a|), one right-hand side per row; both may be column windows of wider storage."""
+	n, q, d, t = a.shape[0], b.shape[0], _ncols(a, cols), Vt.shape[0]
+	work = kmv_workspace(n, q, d, t, Yt) if work is None else work
+	_launch("stpy_kmv", kind, dtype_code(Yt.dtype), ptr(a), n, ld(a), ptr(b), q, ld(b), d, ptr(cols), ptr(inv_ls), float(kappa), float(diag_add),
+			ptr(Vt), t, ld(Vt), ptr(Yt), ld(Yt), ptr(work), work.numel())
+
+
+def pcg_workspace(n, d, t, r, like):
+	"""State and scratch of stpy_pcg for t columns of n points and a rank-r preconditioner: keep it between the calls of one solve."""
+	return _work(load().stpy_pcg_workspace_bytes(dtype_code(like.dtype), n, d, t, r), like)
+
+
+def pcg(kind, x, inv_ls, Bt, Xt, work, out, cols=None, kappa=1.0, diag_add=0.0, Gt=None, Gn=None, tol=0.0, iters=10, init=True):
+	"""``iters`` iterations of block preconditioned CG on (K(x, x) + diag_add I) X_c = B_c, rows of Bt / Xt (t, n) (stpy_pcg in the header).
+	``work`` (pcg_workspace) carries the state from call to call; ``out`` = (relres (t,), bx (t,), its (t,) int32), device tensors written
+	at the end of the call and unread.  Gt (r, n) / Gn (n, r): the preconditioner I - G G^T, or None."""
+	n, d, t = x.shape[0], _ncols(x, cols), Bt.shape[0]
+	r = 0 if Gt is None else Gt.shape[0]
+	relres, bx, its = out
+	_launch("stpy_pcg", kind, dtype_code(Xt.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), float(kappa), float(diag_add),
+			ptr(Gt), ld(Gt) if r else 0, ptr(Gn), ld(Gn) if r else 0, r, ptr(Bt), ld(Bt), ptr(Xt), ld(Xt), t, float(tol), int(iters), int(bool(init)),
+			ptr(relres), ptr(bx), ptr(its), ptr(work), work.numel())
 
 
 def rff_embed(x, W, m, scale, bias=None, feat_scale=None, transposed=False, workspace=False):

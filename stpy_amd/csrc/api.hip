@@ -607,3 +607,6 @@ int stpy_profile_read_union(int tagmask, double* busy_ms, double* total_flops, i
 // alone for the resource-usage checks), compiled as part of THIS translation unit -- whatever builds the library from its list of
 // sources gets the entry points with api.hip, and the exported symbols stay exactly the header's.
 #include "pchol.hip"
+
+// stpy_kmv / stpy_pcg and their workspace queries: the matrix-free product and solver (kmv.hip), compiled here for the same reason.
+#include "kmv.hip"

@@ -17,6 +17,8 @@
 // Traffic: step j reads j * n elements, a run of rank r reads esz * n * r (r - 1) / 2 bytes; the kernel is a streaming read, bounded by
 // HBM once Ft outgrows the Infinity Cache.  The redundant part -- every workgroup gathers Ft[0:j, p] (j scattered lines) and reads all
 // the partials -- is j / (64 V) of that.
+#ifndef STPY_PCHOL_HIP          // (kmv.hip includes this file for the kernel evaluator; api.hip includes both)
+#define STPY_PCHOL_HIP
 #include "common.h"
 
 #include <limits.h>
@@ -270,3 +272,5 @@ int stpy_pchol(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d
 }
 
 }  // extern "C"
+
+#endif  // STPY_PCHOL_HIP
