@@ -472,6 +472,54 @@ int stpy_pcg(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, 
              void* work, int64_t work_bytes, void* stream);
 
 /*
+ * stpy_pcg that also records what the stochastic Lanczos quadrature of IterativeGaussianProcess.log_marginal_estimate needs: the CG scalars are
+ * the Lanczos coefficients of the preconditioned operator.  Same arguments, same workspace query, same kernels, launch sequence and bits in Xt,
+ * relres, bx and its as stpy_pcg; in addition, for column c and iteration it (1-based, as counted by its[c]):
+ *   coef[(c*cap + it-1)*2 + 0] = the step length as applied (the value cast to the matrix type, stored as a double), written by the step kernel;
+ *   coef[(c*cap + it-1)*2 + 1] = the ratio <R, Z>' / <R, Z> applied to the direction AFTER iteration it, written by the direction kernel;
+ *   rz0[c] = <B_c, M^-1 B_c>, written by the first direction kernel (init != 0).
+ * coef: t * cap * 2 doubles, rz0: t doubles, both on the device.  Slots at and beyond its[c] are left untouched, a frozen column writes nothing
+ * (so the ratio after the iteration on which a column converged is not written), and iterations beyond cap write nothing: the host sizes cap =
+ * its iteration limit.  init == 0 continues filling, so that blocks of iterations give the coefficients of one long call.
+ * With a_j, b_j the two entries of slot j-1 and m = its[c], the Lanczos matrix is the symmetric tridiagonal T (m x m) with T[0,0] = 1 / a_1,
+ * T[j,j] = 1 / a_(j+1) + b_j / a_j and T[j,j+1] = sqrt(b_(j+1)) / a_(j+1).
+ * Refused before any HIP call: cap < 1 (-19), NULL coef or rz0 (-3), then everything stpy_pcg refuses.
+ */
+int stpy_pcg_lanczos(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+                     double kappa, double diag_add,
+                     const void* Gt, int64_t ldgt, const void* Gn, int64_t ldgn, int64_t r,
+                     const void* Bt, int64_t ldb, void* Xt, int64_t ldxt, int64_t t,
+                     double tol, int iters, int init,
+                     void* relres, void* bx, int32_t* its,
+                     double* coef, int64_t cap, double* rz0,
+                     void* work, int64_t work_bytes, void* stream);
+
+/*
+ * Bilinear forms of the hyper-parameter derivative of the kernel matrix of stpy_kmv (a == b == x), the matrix never formed: for every pair of
+ * rows c < t of Ut / Vt (t x n), with e_ijk = (x_i - x_j)[cols[k]] * inv_ls[k] (difference first, scale second), rho_ij = sum_k e_ijk^2 (fma, in
+ * coordinate order), phi the kernel profile of stpy_pchol and chi = 2 dphi/drho (SE: -exp(-rho/2); MATERN12: -exp(-r)/r; MATERN32:
+ * -3 exp(-sqrt3 r); MATERN52: -(5/3)(1 + sqrt5 r) exp(-sqrt5 r); r = sqrt(rho)):
+ *   out[c*ldo + k]     = sum_i sum_j Ut[c,i] Vt[c,j] kappa chi(rho_ij) e_ijk^2      k < d     (d(u^T K v) / d inv_ls[k] = out[c,k] / inv_ls[k])
+ *   out[c*ldo + d]     = sum_i sum_j Ut[c,i] Vt[c,j] kappa phi(rho_ij)                        (u^T K v; d / dkappa = out[c,d] / kappa)
+ *   out[c*ldo + d + 1] = sum_i Ut[c,i] Vt[c,i]                                                (d(K + s^2 I) / ds = 2 s I)
+ * A pair with rho == 0 contributes exactly 0 to the first d outputs (no 0 / 0 for MATERN12).  kind, cols, inv_ls, kappa as for stpy_kmv.
+ * A workgroup owns 64 points i and 16 pairs c and walks j in a fixed order; on the 16x16x4 MFMA a lane evaluates rho, phi, chi and the d squares
+ * of the one pair (i, j) its B operand wants and issues d + 1 matrix instructions against the same fragment of Vt.  Coordinates stay in
+ * registers up to d = 16 (instantiations for 4, 8, 16); beyond, a workgroup owns the outputs of one group of 16 coordinates.  One partial row per
+ * workgroup passes through `work`; a second launch adds them in a fixed order (and, with too few workgroups to fill the chip, the pieces the j
+ * range was cut into): no atomics, no spin-waits, no cooperative grid.  Two calls give the same bits, and ldu / ldv / ldo do not change a bit.
+ * Two launches, no host synchronisation, no allocation.
+ * Refused before any HIP call: kind (-1), dtype (-2), NULL x / inv_ls / Ut / Vt / out (-3), n negative or >= 2^31 (-4), ldx < d (-5), d < 1 (-6),
+ * t < 1 or more than 65535 blocks of 16 pairs x ceil(d / 16) coordinate groups (-10), kappa not finite (-11), ldu or ldv < n or ldo < d + 2 (-13),
+ * work not 8-byte aligned (-17), work NULL or work_bytes below stpy_kmv_dtheta_workspace_bytes(dtype, n, d, t) (-20).
+ * n == 0: returns 0, out[c, 0 .. d + 1] = 0 (only out is looked at).
+ */
+int64_t stpy_kmv_dtheta_workspace_bytes(int dtype, int64_t n, int d, int64_t t);
+int stpy_kmv_dtheta(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls, double kappa,
+                    const void* Ut, int64_t ldu, const void* Vt, int64_t ldv, int64_t t,
+                    void* out, int64_t ldo, void* work, int64_t work_bytes, void* stream);
+
+/*
  * Input gradients of the GP posterior (gauss_procc.py:420-459 mean_gradient_hessian / gradient_mean_var and the
  * autograd of mean_std through a test tensor with requires_grad; ucb_optimize, :918-963).  One kernel term k = kappa phi,
  * test points xt (m x ldt) against training points x (n x ldx), scaled differences e = (xt - x_i)[cols] * inv_ls:

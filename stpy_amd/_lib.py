@@ -75,6 +75,10 @@ SIGNATURES = {
 	"stpy_pcg_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64, _i64]),
 	"stpy_pcg": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _dbl, _i32, _i32,
 						_vp, _vp, _vp, _vp, _i64, _vp]),
+	"stpy_pcg_lanczos": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _dbl, _i32, _i32,
+								_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+	"stpy_kmv_dtheta_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
+	"stpy_kmv_dtheta": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
 	"stpy_gram_grad_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i32]),
 	"stpy_gram_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_trsm_ln_factor": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
@@ -490,6 +494,33 @@ def pcg(kind, x, inv_ls, Bt, Xt, work, out, cols=None, kappa=1.0, diag_add=0.0, 
 	_launch("stpy_pcg", kind, dtype_code(Xt.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), float(kappa), float(diag_add),
 			ptr(Gt), ld(Gt) if r else 0, ptr(Gn), ld(Gn) if r else 0, r, ptr(Bt), ld(Bt), ptr(Xt), ld(Xt), t, float(tol), int(iters), int(bool(init)),
 			ptr(relres), ptr(bx), ptr(its), ptr(work), work.numel())
+
+
+def pcg_lanczos(kind, x, inv_ls, Bt, Xt, work, out, coef, rz0, cols=None, kappa=1.0, diag_add=0.0, Gt=None, Gn=None, tol=0.0, iters=10, init=True):
+	"""``pcg`` that also records the CG scalars (stpy_pcg_lanczos in the header): coef (t, cap, 2) float64 -- the step length and the direction
+	ratio of every iteration, as applied -- and rz0 (t,) float64 = <B_c, M^-1 B_c>, device tensors.  Slots from its[c] on are left as they are."""
+	n, d, t = x.shape[0], _ncols(x, cols), Bt.shape[0]
+	r = 0 if Gt is None else Gt.shape[0]
+	relres, bx, its = out
+	if coef.dtype != torch.float64 or rz0.dtype != torch.float64 or not coef.is_contiguous() or coef.shape[0] != t or coef.shape[2] != 2 or rz0.numel() != t:
+		raise StpyHipError("pcg_lanczos: coef must be a contiguous float64 (t, cap, 2) tensor and rz0 a float64 (t,) tensor")
+	_launch("stpy_pcg_lanczos", kind, dtype_code(Xt.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), float(kappa), float(diag_add),
+			ptr(Gt), ld(Gt) if r else 0, ptr(Gn), ld(Gn) if r else 0, r, ptr(Bt), ld(Bt), ptr(Xt), ld(Xt), t, float(tol), int(iters), int(bool(init)),
+			ptr(relres), ptr(bx), ptr(its), ptr(coef), coef.shape[1], ptr(rz0), ptr(work), work.numel())
+
+
+def kmv_dtheta_workspace(n, d, t, like):
+	"""Scratch of stpy_kmv_dtheta (one partial row per workgroup and pair)."""
+	return _work(load().stpy_kmv_dtheta_workspace_bytes(dtype_code(like.dtype), n, d, t), like)
+
+
+def kmv_dtheta(kind, x, inv_ls, Ut, Vt, out, cols=None, kappa=1.0, work=None):
+	"""out[c] = (u_c^T (dK / d inv_ls[k]) v_c * inv_ls[k] for k < d, u_c^T K v_c, <u_c, v_c>) for the rows of Ut / Vt (t, n), K = k(x, x) never
+	formed (stpy_kmv_dtheta in the header).  out: (t, d + 2), may be a column window of wider storage."""
+	n, d, t = x.shape[0], _ncols(x, cols), Ut.shape[0]
+	work = kmv_dtheta_workspace(n, d, t, out) if work is None else work
+	_launch("stpy_kmv_dtheta", kind, dtype_code(out.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), float(kappa), ptr(Ut), ld(Ut), ptr(Vt), ld(Vt), t,
+			ptr(out), ld(out), ptr(work), work.numel())
 
 
 def rff_embed(x, W, m, scale, bias=None, feat_scale=None, transposed=False, workspace=False):

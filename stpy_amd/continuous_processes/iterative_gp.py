@@ -22,12 +22,30 @@ Out of scope, each for its own reason (all raise NotImplementedError before the 
                                    Cholesky preconditioner covers as well;
   Sigma                            a general noise matrix is a second dense N x N operand;
   multi-GPU                        the row split of the operator needs its own reduction of the CG scalars across ranks.
+
+That estimator exists under its own names, ``log_marginal_estimate`` and ``optimize_params_estimate`` (below): a randomised value with a reported
+standard error, never returned where the exact evidence is asked for.
+
+  log_marginal_estimate   stochastic Lanczos quadrature on the preconditioned operator.  Probes z_c = w1_c + F w2_c / s (covariance M, the
+              preconditioner); ONE stpy_pcg_lanczos solve of the rows [y; z_1 .. z_t] gives alpha, u_c = A^-1 z_c and, per column, the CG scalars,
+              which are the Lanczos coefficients: q_c = <z_c, M^-1 z_c> e_1^T (log T_c - log s^2 I) e_1 and
+              log det A ~= mean_c q_c + (n - r) log s^2 + 2 sum log L_ll.  The last two terms are log det(s^2 I + F F^T), exact; the
+              - log s^2 inside q_c is a control variate (it replaces the random <z, M^-1 z> log s^2 by its expectation n log s^2; without it
+              the standard error is several times larger).  Gradient: -1/2 alpha^T dA alpha + 1/2 weight tr~, where tr~ estimates tr(A^-1 dA) =
+              E[u_c^T dA v_c], v_c = M^-1 z_c, with the same idea as a control variate: b_c = v_c^T dA v_c / s^2 has the exactly known mean
+              tr(P^-1 dA) = (tr dA - sum_l g_l^T dA g_l) / s^2 (P = s^2 I + F F^T, g_l the columns of G), and tr~ = mean(a) + beta (E b - mean(b))
+              with the fitted beta (``_control_variate``).  Where the preconditioner is exact the random part vanishes in value AND gradient
+              (an optimiser handed an exact value and a noisy slope stalls); where it is weak beta -> 0.  All bilinear forms come from
+              stpy_kmv_dtheta: one pass over 1 + 2 t pairs and one over the r columns of G.  One evaluation with gradient = one stpy_pchol,
+              one block solve of 1 + t columns, the derivative passes.  The standard error shrinks with 1 / sqrt(num_probes) and with the quality of the preconditioner: the
+              probes only see what the rank-r factor leaves of K (large for a slowly decaying spectrum, e.g. Matern 5/2 at r << n).
 """
 import numpy as np
+import scipy.linalg
 import torch
 
 from .. import _lib
-from ..estimator import Estimator
+from ..estimator import Estimator, Euclidean
 from ..kernels import KernelFunction
 from .nystrom_fea import _stationary_term
 
@@ -41,7 +59,7 @@ _OUT_OF_SCOPE = {
 class IterativeGaussianProcess(Estimator):
 
 	def __init__(self, gamma=1, s=0.001, kappa=1., kernel_name="squared_exponential", d=1, kernel=None,
-				 precond_rank=256, precond_tol=0., tol=None, maxiter=1000, check_every=10, rhs_block=64, nu=1.5):
+				 precond_rank=256, precond_tol=0., tol=None, maxiter=1000, check_every=10, rhs_block=64, nu=1.5, num_probes=16, probe_seed=0):
 		self.s = s
 		self.d = d
 		self.x = self.y = None
@@ -55,6 +73,9 @@ class IterativeGaussianProcess(Estimator):
 		self.kernel = self.kernel_object.kernel
 		self.precond_rank, self.precond_tol = int(precond_rank), float(precond_tol)
 		self.tol, self.maxiter, self.check_every, self.rhs_block = tol, int(maxiter), int(check_every), int(rhs_block)
+		self.num_probes, self.probe_seed = int(num_probes), int(probe_seed)
+		self.evidence_info = None
+		self._probes = None
 		self.trace_error = None
 		self.cg_info = {"iterations": 0, "relres": 0.0, "rank": 0, "kmv_launches": 0}
 		self._xd = self._alpha = self._Gt = self._Gn = None
@@ -70,6 +91,8 @@ class IterativeGaussianProcess(Estimator):
 			raise ValueError("IterativeGaussianProcess: maxiter, check_every and rhs_block must be positive")
 		if self.tol is not None and not float(self.tol) > 0.0:
 			raise ValueError("IterativeGaussianProcess: tol must be positive")
+		if self.num_probes < 2:
+			raise ValueError("IterativeGaussianProcess: num_probes must be at least 2 (the standard error is a sample standard deviation)")
 
 	def description(self):
 		return self.kernel_object.description() + "\nlambda=" + str(self.s) + "\nmatrix-free (preconditioned CG, rank <= %d)" % self.precond_rank
@@ -99,13 +122,18 @@ class IterativeGaussianProcess(Estimator):
 		cols, inv_ls = self.kernel_object._term_operands(t, xd, xd.dtype, xd.device)
 		return t, cols, inv_ls
 
-	def _solve(self, Bt, what):
+	def _solve(self, Bt, what, hyper=None, record=None):
 		"""Xt with (K + s^2 I) Xt[c] = Bt[c] for the rows of Bt (t, N), by stpy_pcg in blocks of ``check_every`` iterations.  Returns (Xt, bx (t,),
-		its (t,) int32 on the host, largest relres).  Raises on a flagged column or when ``maxiter`` iterations do not reach the tolerance."""
+		its (t,) int32 on the host, largest relres).  Raises on a flagged column or when ``maxiter`` iterations do not reach the tolerance.
+		hyper: (term, cols, inv_ls, s, Gt, Gn) of another operator than the fitted one; record: (coef, rz0) for stpy_pcg_lanczos."""
 		xd = self._xd
-		t, cols, inv_ls = self._operands(xd)
+		if hyper is None:
+			t, cols, inv_ls = self._operands(xd)
+			s, Gt, Gn = float(self.s), self._Gt, self._Gn
+		else:
+			t, cols, inv_ls, s, Gt, Gn = hyper
 		nrhs, n = Bt.shape
-		r = 0 if self._Gt is None else self._Gt.shape[0]
+		r = 0 if Gt is None else Gt.shape[0]
 		tol = self._tol(xd.dtype)
 		Xt = torch.empty((nrhs, n), dtype=xd.dtype, device=xd.device)
 		work = _lib.pcg_workspace(n, inv_ls.numel(), nrhs, r, xd)
@@ -114,8 +142,12 @@ class IterativeGaussianProcess(Estimator):
 		done = 0
 		while True:
 			iters = min(self.check_every, self.maxiter - done)
-			_lib.pcg(t['kind'], xd, inv_ls, Bt, Xt, work, out, cols=cols, kappa=t['kappa'], diag_add=float(self.s) ** 2, Gt=self._Gt, Gn=self._Gn,
-					 tol=tol, iters=iters, init=done == 0)
+			if record is None:
+				_lib.pcg(t['kind'], xd, inv_ls, Bt, Xt, work, out, cols=cols, kappa=t['kappa'], diag_add=s ** 2, Gt=Gt, Gn=Gn,
+						 tol=tol, iters=iters, init=done == 0)
+			else:
+				_lib.pcg_lanczos(t['kind'], xd, inv_ls, Bt, Xt, work, out, record[0], record[1], cols=cols, kappa=t['kappa'], diag_add=s ** 2, Gt=Gt, Gn=Gn,
+								 tol=tol, iters=iters, init=done == 0)
 			done += iters
 			self._kmv_launches += iters
 			relres, its = out[0].cpu().numpy(), out[2].cpu().numpy()          # the block's synchronisation
@@ -129,6 +161,227 @@ class IterativeGaussianProcess(Estimator):
 			if done >= self.maxiter:
 				raise RuntimeError("IterativeGaussianProcess.%s: no convergence in maxiter=%d iterations: relative residual %.3e, tolerance %.3e "
 								   "(raise maxiter or precond_rank)" % (what, self.maxiter, worst, tol))
+
+	def _preconditioner(self, t, cols, inv_ls, s, probes_w2=None, Z=None):
+		"""(rank, Gn, Gt, sum log L_ll (with Z only), trace word) of the rank <= precond_rank preconditioner for the given operands; with Z (t, N) and
+		probes_w2 (t, >= rank) also Z += w2 F^T / s (one stpy_gemm_nt on the factor, before it is overwritten by G)."""
+		xd = self._xd
+		n = xd.shape[0]
+		m = min(self.precond_rank, n)
+		if m < 1:
+			return 0, None, None, 0.0, None
+		piv, Ft, dres, rank_dev = _lib.pchol(t['kind'], xd, inv_ls, m, cols=cols, kappa=t['kappa'], tol=self.precond_tol)
+		trace = _lib.trace_dot(u=dres, v=torch.ones_like(dres))[1]            # sum of the residual diagonal, fixed order; unread
+		rank = int(rank_dev.item())
+		if rank < 1:
+			return 0, None, None, 0.0, trace
+		Ft = Ft[:rank]
+		C = torch.empty((rank, rank), dtype=xd.dtype, device=xd.device)
+		_lib.syrk(Ft, C)                                                # F^T F on the lower tiles
+		_lib.combine(C, C, _lib.OUT_SET, s ** 2)                        # + s^2 I
+		winv, info = _lib.potrf(C)
+		Gn = Ft.t().contiguous()                                        # F (N, r)
+		if Z is not None:
+			_lib.gemm_nt((probes_w2[:, :rank] / s).contiguous(), Gn, Z, 2)
+		_lib.trsm_right_lt(Gn, C, winv)                                 # G = F L^-T
+		bad = int(info.item())
+		if bad != 0:
+			raise torch.linalg.LinAlgError("IterativeGaussianProcess: the preconditioner's s^2 I + F^T F is not positive definite (leading minor %d of %d)" % (bad, rank))
+		sumlog = float(_lib.logdet_quad(C)[0].item()) if Z is not None else 0.0          # (the estimate's exact part; the fit has no use for it)
+		return rank, Gn, Gn.t().contiguous(), sumlog, trace
+
+	# ------------------------------------------------------------------ the stochastic evidence
+	_X_KEYS = ("gamma", "ard_gamma", "kappa", "group", "offset", "nu")
+
+	def _check_overrides(self, kernel, X):
+		"""Host refusals of log_marginal_estimate; returns (X, the one stationary term it resolves to)."""
+		X = {} if X is None else X
+		if kernel is not self.kernel_object:
+			_stationary_term(kernel)
+		for key, item in X.items():
+			if str(key) != "0" or not isinstance(item, dict):
+				raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: overrides for kernel item %r; the matrix-free operator has ONE item, '0'" % (key,))
+			for name, v in item.items():
+				if name not in self._X_KEYS:
+					raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: override %r is not a lengthscale of a single stationary term "
+											  "(supported: 'gamma' / 'ard_gamma'; the stored %s pass through unchanged)" % (name, ", ".join(repr(k) for k in self._X_KEYS[2:])))
+				if name not in ("gamma", "ard_gamma") and torch.is_tensor(v) and v.requires_grad:
+					raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: no gradient with respect to %r (lengthscales and the noise only)" % name)
+		items = kernel._chain(X if X else None)
+		if len(items) != 1 or len(items[0]['terms']) != 1:
+			raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: the overrides resolve to %d items; ONE stationary term is supported" % len(items))
+		return X, items[0]['terms'][0]
+
+	def _grad_params(self, X):
+		"""(key, name, tensor) for every hyper-parameter tensor that asks for a gradient (the convention of GaussianProcess)."""
+		out = []
+		for key in sorted(X.keys()):
+			for name in ("gamma", "ard_gamma"):
+				v = X[key].get(name)
+				if torch.is_tensor(v) and v.requires_grad:
+					out.append((key, name, v))
+		if torch.is_tensor(self.s) and self.s.requires_grad:
+			out.append(("likelihood", "sigma", self.s))
+		return out
+
+	def _probe_draws(self, n, dtype, device, probes):
+		width = n + min(self.precond_rank, n)
+		if probes is not None:
+			W = torch.as_tensor(probes)
+			if W.dim() != 2 or W.shape[0] < 2 or W.shape[1] < width:
+				raise ValueError("IterativeGaussianProcess.log_marginal_estimate: probes must be (t >= 2, n + precond_rank = %d) standard normal draws, got %s"
+								 % (width, tuple(W.shape)))
+			return W.to(device=device, dtype=dtype)
+		key = (n, width, self.num_probes, self.probe_seed, dtype)
+		if self._probes is None or self._probes[0] != key:
+			gen = torch.Generator(device="cpu").manual_seed(self.probe_seed)
+			W = torch.randn((self.num_probes, width), generator=gen, dtype=torch.float64)
+			self._probes = (key, W.to(device=device, dtype=dtype))          # drawn once per object and data size: common random numbers
+		return self._probes[1]
+
+	def log_marginal_estimate(self, kernel=None, X=None, weight=1.0, probes=None):
+		"""A stochastic estimate of GaussianProcess.log_marginal's value 1/2 y^T A^-1 y + 1/2 weight log det A, A = K_theta + s^2 I, shape (1, 1),
+		placed like the data (the module docstring states the estimator).  ``X``: overrides of the single kernel item, {'0': {'gamma' |
+		'ard_gamma': tensor}}.  If a lengthscale tensor in ``X`` or ``self.s`` requires grad the result carries an autograd node whose backward is
+		the estimated gradient.  Needs data (fit_gp); does its own stpy_pchol and solve for the hyper-parameters asked about and leaves the
+		fitted state untouched.  ``probes``: (t, n + precond_rank) standard normal draws, columns [0, n) = w1, then w2; default: ``num_probes``
+		rows drawn once from ``probe_seed`` and reused, so that the estimate is a deterministic function of the hyper-parameters.
+		``self.evidence_info``: value, stderr, logdet, logdet_stderr, grad_stderr ({parameter name: array}, None without a gradient), probes,
+		iterations, rank, kmv_launches, and q, the per-probe quadratures.  Standard errors are sample standard deviations / sqrt(t): they
+		measure the probe variance, not the (much smaller) quadrature error."""
+		kernel = self.kernel_object if kernel is None else kernel
+		if self.num_probes < 2:
+			raise ValueError("IterativeGaussianProcess: num_probes must be at least 2 (the standard error is a sample standard deviation)")
+		X, term = self._check_overrides(kernel, X)
+		if self.x is None or self.y is None:
+			raise AttributeError("IterativeGaussianProcess.log_marginal_estimate needs data: call fit_gp first")
+		params = self._grad_params(X)
+		if params:
+			return _EstimateFn.apply(self, term, weight, probes, params, *[t for (_, _, t) in params])
+		return self._estimate(term, weight, probes, [])[0]
+
+	def _estimate(self, term, weight, probes, params):
+		"""(value (1, 1), [gradient per entry of params])."""
+		if self._xd is None:
+			self._xd = _lib.to_device(self.x)
+		xd = self._xd
+		n = xd.shape[0]
+		yd = _lib.to_device(self.y, xd.dtype).reshape(1, -1)
+		s = float(self.s)
+		w = float(weight.item()) if torch.is_tensor(weight) else float(weight)
+		cols, inv_ls = self.kernel_object._term_operands(term, xd, xd.dtype, xd.device)
+		W = self._probe_draws(n, xd.dtype, xd.device, probes)
+		t = W.shape[0]
+		Bt = torch.empty((1 + t, n), dtype=xd.dtype, device=xd.device)
+		Bt[0] = yd[0]
+		Bt[1:] = W[:, :n]
+		rank, Gn, Gt, sumlog, _ = self._preconditioner(term, cols, inv_ls, s, probes_w2=W[:, n:], Z=Bt[1:])
+		coef = torch.full((1 + t, self.maxiter, 2), float("nan"), dtype=torch.float64, device=xd.device)
+		rz0 = torch.zeros((1 + t,), dtype=torch.float64, device=xd.device)
+		launches = self._kmv_launches
+		try:
+			Xt, bx, its, worst = self._solve(Bt, "log_marginal_estimate", hyper=(term, cols, inv_ls, s, Gt, Gn), record=(coef, rz0))
+		finally:
+			used, self._kmv_launches = self._kmv_launches - launches, launches
+		out = outg = None
+		if params:
+			# the derivative pass: rows [alpha; u_c; v_c] against rows [alpha; v_c; v_c], v_c = M^-1 z_c by the two NT products of the solver;
+			# then the columns of G against themselves (the control variate's exact expectation)
+			d = inv_ls.numel()
+			Ut = torch.empty((1 + 2 * t, n), dtype=xd.dtype, device=xd.device)
+			Vt = torch.empty((1 + 2 * t, n), dtype=xd.dtype, device=xd.device)
+			Ut[:1 + t] = Xt
+			Vt[0] = Xt[0]
+			Vt[1:1 + t] = Bt[1:]
+			if rank > 0:
+				Wr = torch.empty((t, rank), dtype=xd.dtype, device=xd.device)
+				_lib.gemm_nt(Bt[1:], Gt, Wr)
+				_lib.gemm_nt(Wr, Gn, Vt[1:1 + t], 1)
+			Vt[1 + t:] = Vt[1:1 + t]
+			Ut[1 + t:] = Vt[1:1 + t]
+			out = torch.empty((1 + 2 * t, d + 2), dtype=xd.dtype, device=xd.device)
+			_lib.kmv_dtheta(term['kind'], xd, inv_ls, Ut, Vt, out, cols=cols, kappa=term['kappa'])
+			used += 1
+			outg = np.zeros((0, d + 2))
+			if rank > 0:
+				og = torch.empty((rank, d + 2), dtype=xd.dtype, device=xd.device)
+				_lib.kmv_dtheta(term['kind'], xd, inv_ls, Gt, Gt, og, cols=cols, kappa=term['kappa'])
+				used += 1
+				outg = og.double().cpu().numpy()
+			out = out.double().cpu().numpy()
+		# host: at most 1 + t tridiagonal eigenproblems of order its
+		coef_h, rz0_h, yalpha = coef[1:].cpu().numpy(), rz0[1:].cpu().numpy(), float(bx[0].item())
+		q = np.zeros(t)
+		for c in range(t):
+			m = int(its[1 + c])
+			if m < 1:
+				continue                                                   # (a zero probe: q = 0)
+			a, b = coef_h[c, :m, 0], coef_h[c, :m - 1, 1]
+			dg = 1.0 / a
+			dg[1:] += b / a[:-1]
+			if m > 1:
+				theta, V = scipy.linalg.eigh_tridiagonal(dg, np.sqrt(b) / a[:-1], lapack_driver="stev")          # (QR iteration: the default MRRR driver gave up on the clustered Ritz values of an 800-step run)
+				q[c] = rz0_h[c] * float(np.sum(V[0] ** 2 * (np.log(theta) - np.log(s * s))))
+			else:
+				q[c] = rz0_h[c] * (np.log(dg[0]) - np.log(s * s))
+		sem = lambda v: float(np.std(v, ddof=1) / np.sqrt(len(v)))
+		logdet = float(q.mean()) + (n - rank) * np.log(s * s) + 2.0 * sumlog
+		value = 0.5 * yalpha + 0.5 * w * logdet
+		grads, gse = [], None
+		if params:
+			il = np.asarray(term['inv_ls'], dtype=np.float64)
+			gse = {}
+			for (key, name, tensor) in params:
+				if key == "likelihood":                                     # dA/ds = 2 s I; tr(P^-1) = (n - |G|_F^2) / s^2
+					rows, rowsg, tr_dA = 2.0 * s * out[:, d + 1:d + 2], 2.0 * s * outg[:, d + 1:d + 2], np.array([2.0 * s * n])
+					shown = "sigma"
+				else:
+					if term['pname'] != name:
+						raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: the kernel has no '%s' lengthscale" % name)
+					# d/d gamma_p = sum over the coordinates k that gamma_p scales of (out[c, k] / inv_ls[k]) * (-inv_ls[k]^2); tr(dK/dgamma) = 0
+					rows, rowsg = np.zeros((1 + 2 * t, tensor.numel())), np.zeros((outg.shape[0], tensor.numel()))
+					for k, pk in enumerate(term['pidx']):
+						rows[:, int(pk)] -= out[:, k] * il[k]
+						rowsg[:, int(pk)] -= outg[:, k] * il[k]
+					tr_dA, shown = np.zeros(rows.shape[1]), name
+				g, se = np.zeros(rows.shape[1]), np.zeros(rows.shape[1])
+				for j in range(rows.shape[1]):
+					tr, se_j = _control_variate(rows[1:1 + t, j], rows[1 + t:, j] / (s * s), (tr_dA[j] - rowsg[:, j].sum()) / (s * s))
+					g[j], se[j] = -0.5 * rows[0, j] + 0.5 * w * tr, 0.5 * w * se_j
+				gse[shown] = se
+				grads.append(torch.from_numpy(g).reshape(tensor.shape if tensor.dim() > 0 else ()).to(device=tensor.device, dtype=tensor.dtype))
+		self.evidence_info = {"value": value, "stderr": 0.5 * w * sem(q), "logdet": logdet, "logdet_stderr": sem(q), "grad_stderr": gse, "probes": t,
+							  "iterations": int(its.max()), "rank": rank, "kmv_launches": used, "q": q}
+		val = torch.full((1, 1), value, dtype=xd.dtype, device=xd.device)
+		return _lib.like_input(val, self.x), grads
+
+	def optimize_params_estimate(self, type='bandwidth', restarts=10, regularizer=None, maxiter=1000, mingradnorm=1e-4, verbose=False,
+								 optimizer="pytorch-minimize", scale=1., weight=1., save=False, save_name='model.np', init_func=None, bounds=None,
+								 parallel=False, cores=None):
+		"""GaussianProcess.optimize_params with ``log_marginal_estimate`` for the objective: the same parameter dictionary ('gamma' / 'ard_gamma'
+		of the item, with "bandwidth+noise" also the noise std) through Estimator.optimize_params_general, which writes the best point back
+		and refits.  ``parallel=True`` is accepted and runs serially.
+		The probes are fixed (common random numbers), so the objective is a deterministic function; but the value estimate and the gradient
+		estimate are two estimators of neighbouring quantities, not an exact derivative pair: a line search can stall where they disagree by
+		more than the decrease it asks for.  Raise ``num_probes`` or ``precond_rank`` (both shrink the standard errors in ``evidence_info``)
+		when that happens."""
+		if type not in ("bandwidth", "bandwidth+noise"):
+			raise NotImplementedError("IterativeGaussianProcess.optimize_params_estimate(type='%s'): 'bandwidth' and 'bandwidth+noise' only" % type)
+		if regularizer is not None:
+			raise NotImplementedError("IterativeGaussianProcess.optimize_params_estimate: no regularizer")
+		params = {}
+		for key, dict2 in self.kernel_object.params_dict.items():
+			if 'gamma' in dict2.keys():
+				params[key] = {'gamma': (init_func, Euclidean(1), bounds)}
+			elif 'ard_gamma' in dict2.keys():
+				params[key] = {'ard_gamma': (init_func, Euclidean(len(dict2['group'])), bounds)}
+		if type == "bandwidth+noise":
+			s0 = self.s
+			params['likelihood'] = {'sigma': ((lambda k: s0), Euclidean(1), None)}
+		view = _EstimateView.__new__(_EstimateView)
+		view.__dict__ = self.__dict__                                       # the same state: what the driver writes lands on this object
+		return view.optimize_params_general(params=params, restarts=restarts, optimizer=optimizer, maxiter=maxiter, mingradnorm=mingradnorm,
+											verbose=verbose, scale=scale, weight=weight, save=save, save_name=save_name, parallel=False, cores=cores)
 
 	# ------------------------------------------------------------------ fit
 	def fit(self, x=None, y=None):
@@ -148,26 +401,8 @@ class IterativeGaussianProcess(Estimator):
 		self._kmv_launches = 0
 		xd = self._xd = _lib.to_device(x)
 		yd = _lib.to_device(y, xd.dtype).reshape(1, -1)
-		n = xd.shape[0]
 		t, cols, inv_ls = self._operands(xd)
-		rank = 0
-		m = min(self.precond_rank, n)
-		if m > 0:
-			piv, Ft, dres, rank_dev = _lib.pchol(t['kind'], xd, inv_ls, m, cols=cols, kappa=t['kappa'], tol=self.precond_tol)
-			self.trace_error = _lib.trace_dot(u=dres, v=torch.ones_like(dres))[1]          # sum of the residual diagonal, fixed order; unread
-			rank = int(rank_dev.item())
-		if rank > 0:
-			Ft = Ft[:rank]
-			C = torch.empty((rank, rank), dtype=xd.dtype, device=xd.device)
-			_lib.syrk(Ft, C)                                                # F^T F on the lower tiles
-			_lib.combine(C, C, _lib.OUT_SET, float(self.s) ** 2)            # + s^2 I
-			winv, info = _lib.potrf(C)
-			Gn = Ft.t().contiguous()                                        # F (N, r)
-			_lib.trsm_right_lt(Gn, C, winv)                                 # G = F L^-T
-			bad = int(info.item())
-			if bad != 0:
-				raise torch.linalg.LinAlgError("IterativeGaussianProcess: the preconditioner's s^2 I + F^T F is not positive definite (leading minor %d of %d)" % (bad, rank))
-			self._Gn, self._Gt = Gn, Gn.t().contiguous()
+		rank, self._Gn, self._Gt, _, self.trace_error = self._preconditioner(t, cols, inv_ls, float(self.s))
 		Xt, _, its, worst = self._solve(yd, "fit_gp")
 		self._alpha = Xt.reshape(-1)
 		self.cg_info = {"iterations": int(its.max()), "relres": worst, "rank": rank, "kmv_launches": self._kmv_launches}
@@ -240,3 +475,38 @@ class IterativeGaussianProcess(Estimator):
 	def ucb(self, xtest):
 		mu, s = self.mean_std(xtest)
 		return mu + 2 * s
+
+
+def _control_variate(a, b, Eb):
+	"""(estimate, standard error) of E[a] from paired samples a_c = u_c^T dA v_c and b_c = v_c^T dA v_c / s^2 with E[b] = tr(P^-1 dA) = Eb known
+	exactly (P = s^2 I + F F^T): the regression estimator mean(a) + beta (Eb - mean(b)), beta = cov(a, b) / var(b) from the samples (0 with fewer
+	than 4 samples or a constant b); standard error = the residual standard deviation (two fitted constants) / sqrt(t).  Where the
+	preconditioner is exact a_c = b_c and the random part vanishes, as it does in the value; where it is weak beta -> 0."""
+	t = len(a)
+	vb = float(np.var(b, ddof=1)) if t >= 4 else 0.0
+	beta = float(np.cov(a, b)[0, 1] / vb) if vb > 0 else 0.0
+	res = a - beta * b
+	return float(a.mean() + beta * (Eb - b.mean())), float(np.std(res, ddof=2 if beta != 0.0 else 1) / np.sqrt(t))
+
+
+class _EstimateFn(torch.autograd.Function):
+	"""Autograd node of IterativeGaussianProcess.log_marginal_estimate: value and gradient estimates come from the same solve."""
+
+	@staticmethod
+	def forward(ctx, gp, term, weight, probes, params, *tensors):
+		val, grads = gp._estimate(term, weight, probes, params)
+		ctx.grads = grads
+		return val.clone()
+
+	@staticmethod
+	def backward(ctx, gout):
+		scale = gout.reshape(-1)[0]
+		return (None, None, None, None, None) + tuple(scale.to(g.device) * g for g in ctx.grads)
+
+
+class _EstimateView(IterativeGaussianProcess):
+	"""The estimator as Estimator.optimize_params_general sees it inside optimize_params_estimate: its ``log_marginal`` is the estimate.  Shares
+	the state of the object it views (same __dict__); the public class goes on refusing ``log_marginal``."""
+
+	def log_marginal(self, kernel, X, weight):
+		return self.log_marginal_estimate(kernel, X, weight)

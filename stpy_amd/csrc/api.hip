@@ -610,3 +610,6 @@ int stpy_profile_read_union(int tagmask, double* busy_ms, double* total_flops, i
 
 // stpy_kmv / stpy_pcg and their workspace queries: the matrix-free product and solver (kmv.hip), compiled here for the same reason.
 #include "kmv.hip"
+
+// stpy_kmv_dtheta and its workspace query: the matrix-free hyper-parameter derivative (kmvgrad.hip), compiled here for the same reason.
+#include "kmvgrad.hip"

@@ -268,6 +268,10 @@ struct PcgState {
 	PcgCol* col; int32_t* its; int32_t* frozen; T* R; T* P; T* Z; T* Q; T* W; void* kwork;
 };
 
+// What stpy_pcg_lanczos records on top of the solve (all NULL for stpy_pcg): per column and iteration the step length and the direction ratio
+// as applied, coef[(c * cap + it - 1) * 2 + {0, 1}], and rz0[c] = <B_c, M^-1 B_c>.  They are the Lanczos coefficients of the preconditioned operator.
+struct PcgRec { double* coef; int64_t cap; double* rz0; };
+
 inline int64_t pcg_align(int64_t b) { return (b + 255) / 256 * 256; }
 
 inline int64_t pcg_workspace_bytes(int dtype, int64_t n, int64_t t, int64_t r)
@@ -337,7 +341,7 @@ void pcg_init_kernel(PcgState<T> s, int n, const T* Bt, int64_t ldb, T* Xt, int6
 // pq = <P, Q>; X += alpha P, R -= alpha Q, Z = R, rr = <R, R>; the column freezes on convergence or on a curvature that is not positive and finite
 template <typename T>
 __global__ __launch_bounds__(KM_THREADS)
-void pcg_step_kernel(PcgState<T> s, int n, T* Xt, int64_t ldxt, double tol2)
+void pcg_step_kernel(PcgState<T> s, int n, T* Xt, int64_t ldxt, double tol2, PcgRec rec)
 {
 	__shared__ double red[4];
 	const int c = blockIdx.x;
@@ -361,6 +365,7 @@ void pcg_step_kernel(PcgState<T> s, int n, T* Xt, int64_t ldxt, double tol2)
 		return;
 	}
 	const T alpha = (T)(col.rz / pq);
+	if (rec.coef && threadIdx.x == 0 && it <= rec.cap) rec.coef[((int64_t)c * rec.cap + it - 1) * 2] = (double)alpha;
 	double rr = 0.0;
 	for (int i = threadIdx.x; i < n; i += KM_THREADS) {
 		X[i] = pc_fma(alpha, P[i], X[i]);
@@ -379,7 +384,7 @@ void pcg_step_kernel(PcgState<T> s, int n, T* Xt, int64_t ldxt, double tol2)
 // rz' = <R, Z>; P = Z + (rz' / rz) P (first: P = Z).  A preconditioned residual product that is not positive and finite is flagged like a curvature.
 template <typename T>
 __global__ __launch_bounds__(KM_THREADS)
-void pcg_dir_kernel(PcgState<T> s, int n, int first)
+void pcg_dir_kernel(PcgState<T> s, int n, int first, PcgRec rec)
 {
 	__shared__ double red[4];
 	const int c = blockIdx.x;
@@ -395,6 +400,11 @@ void pcg_dir_kernel(PcgState<T> s, int n, int first)
 		return;
 	}
 	const T beta = first ? (T)0 : (T)(rz / s.col[c].rz);
+	if (rec.coef && threadIdx.x == 0) {
+		const int it = s.its[c];
+		if (first) rec.rz0[c] = rz;
+		else if (it <= rec.cap) rec.coef[((int64_t)c * rec.cap + it - 1) * 2 + 1] = (double)beta;
+	}
 	for (int i = threadIdx.x; i < n; i += KM_THREADS) P[i] = pc_fma(beta, P[i], Z[i]);
 	__syncthreads();                                                  // (every thread has read the old rz)
 	if (threadIdx.x == 0) s.col[c].rz = rz;
@@ -432,7 +442,7 @@ int pcg_precond(const PcgState<T>& s, int64_t n, int64_t t, int64_t r, const T* 
 template <typename T>
 int pcg(int kind, const T* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const T* inv_ls, double kappa, double diag_add,
         const T* Gt, int64_t ldgt, const T* Gn, int64_t ldgn, int64_t r, const T* Bt, int64_t ldb, T* Xt, int64_t ldxt, int64_t t,
-        double tol, int iters, int init, T* relres, T* bx, int32_t* its, void* work, hipStream_t st)
+        double tol, int iters, int init, T* relres, T* bx, int32_t* its, void* work, hipStream_t st, PcgRec rec, const char* name)
 {
 	const PcgState<T> s = pcg_carve<T>(work, n, t, r);
 	const dim3 grid((unsigned)t), block(KM_THREADS);
@@ -441,16 +451,16 @@ int pcg(int kind, const T* x, int64_t n, int64_t ldx, int d, const int32_t* cols
 	if (init) {
 		hipLaunchKernelGGL(pcg_init_kernel<T>, grid, block, 0, st, s, (int)n, Bt, ldb, Xt, ldxt, tol2);
 		if ((rc = pcg_precond<T>(s, n, t, r, Gt, ldgt, Gn, ldgn, st)) != 0) return rc;
-		hipLaunchKernelGGL(pcg_dir_kernel<T>, grid, block, 0, st, s, (int)n, 1);
+		hipLaunchKernelGGL(pcg_dir_kernel<T>, grid, block, 0, st, s, (int)n, 1, rec);
 	}
 	for (int k = 0; k < iters; ++k) {
 		if ((rc = kmv<T>(kind, x, n, ldx, x, n, ldx, d, cols, inv_ls, kappa, diag_add, s.P, t, n, s.Q, n, s.kwork, st)) != 0) return rc;
-		hipLaunchKernelGGL(pcg_step_kernel<T>, grid, block, 0, st, s, (int)n, Xt, ldxt, tol2);
+		hipLaunchKernelGGL(pcg_step_kernel<T>, grid, block, 0, st, s, (int)n, Xt, ldxt, tol2, rec);
 		if ((rc = pcg_precond<T>(s, n, t, r, Gt, ldgt, Gn, ldgn, st)) != 0) return rc;
-		hipLaunchKernelGGL(pcg_dir_kernel<T>, grid, block, 0, st, s, (int)n, 0);
+		hipLaunchKernelGGL(pcg_dir_kernel<T>, grid, block, 0, st, s, (int)n, 0, rec);
 	}
 	hipLaunchKernelGGL(pcg_finish_kernel<T>, grid, block, 0, st, s, (int)n, Bt, ldb, (const T*)Xt, ldxt, relres, bx, its);
-	return check_launch("stpy_pcg");
+	return check_launch(name);
 }
 
 inline bool km_finite(double v) { return v >= -1.79769313486231570e308 && v <= 1.79769313486231570e308; }
@@ -461,6 +471,43 @@ inline bool km_finite(double v) { return v >= -1.79769313486231570e308 && v <= 1
 
 // ---- C ABI (include/stpy_hip.h); every refusal below comes before the first HIP call
 using namespace stpy;
+
+static int pcg_checked(const char* name, int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+                       double kappa, double diag_add,
+                       const void* Gt, int64_t ldgt, const void* Gn, int64_t ldgn, int64_t r,
+                       const void* Bt, int64_t ldb, void* Xt, int64_t ldxt, int64_t t,
+                       double tol, int iters, int init,
+                       void* relres, void* bx, int32_t* its,
+                       void* work, int64_t work_bytes, void* stream, PcgRec rec)
+{
+	if (kind < STPY_K_SE || kind > STPY_K_MATERN52) { set_error("%s: kernel kind %d is not stationary (SE, MATERN12/32/52)", name, kind); return -1; }
+	if (dtype != STPY_F64 && dtype != STPY_F32) { set_error("%s: unknown dtype %d (0 = float64, 1 = float32)", name, dtype); return -2; }
+	if (n < 0 || n >= ((int64_t)1 << 31)) { set_error("%s: n=%lld outside [0, 2^31)", name, (long long)n); return -4; }
+	if (n == 0) return 0;          // empty problem: nothing to write
+	if (d < 1) { set_error("%s: d=%d", name, d); return -6; }
+	if (t < 1 || t > 65535) { set_error("%s: t=%lld outside [1, 65535]", name, (long long)t); return -10; }
+	if (ldx < d) { set_error("%s: ldx=%lld below d=%d", name, (long long)ldx, d); return -5; }
+	if (ldb < n || ldxt < n) { set_error("%s: ldb=%lld or ldxt=%lld below n=%lld", name, (long long)ldb, (long long)ldxt, (long long)n); return -13; }
+	if (!km_finite(kappa) || !km_finite(diag_add)) { set_error("%s: kappa=%g and diag_add=%g must be finite", name, kappa, diag_add); return -11; }
+	if (!(tol >= 0.0) || !km_finite(tol)) { set_error("%s: tol=%g must be finite and not negative", name, tol); return -14; }
+	if (iters < 0) { set_error("%s: iters=%d", name, iters); return -15; }
+	if (r < 0 || r >= ((int64_t)1 << 31)) { set_error("%s: r=%lld outside [0, 2^31)", name, (long long)r); return -16; }
+	if (r > 0 && (!Gt || !Gn)) { set_error("%s: r=%lld with a null Gt or Gn", name, (long long)r); return -3; }
+	if (r > 0 && (ldgt < n || ldgn < r)) { set_error("%s: ldgt=%lld below n=%lld or ldgn=%lld below r=%lld", name, (long long)ldgt, (long long)n, (long long)ldgn, (long long)r); return -18; }
+	if (!x || !inv_ls || !Bt || !Xt || !relres || !bx || !its) { set_error("%s: null pointer", name); return -3; }
+	const int64_t need = pcg_workspace_bytes(dtype, n, t, r);
+	if (!work || work_bytes < need) {
+		set_error("%s: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", name, (long long)(work ? work_bytes : 0), (long long)need);
+		return -20;
+	}
+	if ((uintptr_t)work & 15) { set_error("%s: work must be 16-byte aligned", name); return -17; }
+	hipStream_t st = (hipStream_t)stream;
+	if (dtype == STPY_F64)
+		return pcg<double>(kind, (const double*)x, n, ldx, d, cols, (const double*)inv_ls, kappa, diag_add, (const double*)Gt, ldgt, (const double*)Gn, ldgn, r,
+		                   (const double*)Bt, ldb, (double*)Xt, ldxt, t, tol, iters, init, (double*)relres, (double*)bx, its, work, st, rec, name);
+	return pcg<float>(kind, (const float*)x, n, ldx, d, cols, (const float*)inv_ls, kappa, diag_add, (const float*)Gt, ldgt, (const float*)Gn, ldgn, r,
+	                  (const float*)Bt, ldb, (float*)Xt, ldxt, t, tol, iters, init, (float*)relres, (float*)bx, its, work, st, rec, name);
+}
 
 extern "C" {
 
@@ -513,33 +560,23 @@ int stpy_pcg(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, 
              void* relres, void* bx, int32_t* its,
              void* work, int64_t work_bytes, void* stream)
 {
-	if (kind < STPY_K_SE || kind > STPY_K_MATERN52) { set_error("stpy_pcg: kernel kind %d is not stationary (SE, MATERN12/32/52)", kind); return -1; }
-	if (dtype != STPY_F64 && dtype != STPY_F32) { set_error("stpy_pcg: unknown dtype %d (0 = float64, 1 = float32)", dtype); return -2; }
-	if (n < 0 || n >= ((int64_t)1 << 31)) { set_error("stpy_pcg: n=%lld outside [0, 2^31)", (long long)n); return -4; }
-	if (n == 0) return 0;          // empty problem: nothing to write
-	if (d < 1) { set_error("stpy_pcg: d=%d", d); return -6; }
-	if (t < 1 || t > 65535) { set_error("stpy_pcg: t=%lld outside [1, 65535]", (long long)t); return -10; }
-	if (ldx < d) { set_error("stpy_pcg: ldx=%lld below d=%d", (long long)ldx, d); return -5; }
-	if (ldb < n || ldxt < n) { set_error("stpy_pcg: ldb=%lld or ldxt=%lld below n=%lld", (long long)ldb, (long long)ldxt, (long long)n); return -13; }
-	if (!km_finite(kappa) || !km_finite(diag_add)) { set_error("stpy_pcg: kappa=%g and diag_add=%g must be finite", kappa, diag_add); return -11; }
-	if (!(tol >= 0.0) || !km_finite(tol)) { set_error("stpy_pcg: tol=%g must be finite and not negative", tol); return -14; }
-	if (iters < 0) { set_error("stpy_pcg: iters=%d", iters); return -15; }
-	if (r < 0 || r >= ((int64_t)1 << 31)) { set_error("stpy_pcg: r=%lld outside [0, 2^31)", (long long)r); return -16; }
-	if (r > 0 && (!Gt || !Gn)) { set_error("stpy_pcg: r=%lld with a null Gt or Gn", (long long)r); return -3; }
-	if (r > 0 && (ldgt < n || ldgn < r)) { set_error("stpy_pcg: ldgt=%lld below n=%lld or ldgn=%lld below r=%lld", (long long)ldgt, (long long)n, (long long)ldgn, (long long)r); return -18; }
-	if (!x || !inv_ls || !Bt || !Xt || !relres || !bx || !its) { set_error("stpy_pcg: null pointer"); return -3; }
-	const int64_t need = pcg_workspace_bytes(dtype, n, t, r);
-	if (!work || work_bytes < need) {
-		set_error("stpy_pcg: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", (long long)(work ? work_bytes : 0), (long long)need);
-		return -20;
-	}
-	if ((uintptr_t)work & 15) { set_error("stpy_pcg: work must be 16-byte aligned"); return -17; }
-	hipStream_t st = (hipStream_t)stream;
-	if (dtype == STPY_F64)
-		return pcg<double>(kind, (const double*)x, n, ldx, d, cols, (const double*)inv_ls, kappa, diag_add, (const double*)Gt, ldgt, (const double*)Gn, ldgn, r,
-		                   (const double*)Bt, ldb, (double*)Xt, ldxt, t, tol, iters, init, (double*)relres, (double*)bx, its, work, st);
-	return pcg<float>(kind, (const float*)x, n, ldx, d, cols, (const float*)inv_ls, kappa, diag_add, (const float*)Gt, ldgt, (const float*)Gn, ldgn, r,
-	                  (const float*)Bt, ldb, (float*)Xt, ldxt, t, tol, iters, init, (float*)relres, (float*)bx, its, work, st);
+	return pcg_checked("stpy_pcg", kind, dtype, x, n, ldx, d, cols, inv_ls, kappa, diag_add, Gt, ldgt, Gn, ldgn, r, Bt, ldb, Xt, ldxt, t, tol, iters, init,
+	                   relres, bx, its, work, work_bytes, stream, PcgRec{nullptr, 0, nullptr});
+}
+
+int stpy_pcg_lanczos(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d, const int32_t* cols, const void* inv_ls,
+                     double kappa, double diag_add,
+                     const void* Gt, int64_t ldgt, const void* Gn, int64_t ldgn, int64_t r,
+                     const void* Bt, int64_t ldb, void* Xt, int64_t ldxt, int64_t t,
+                     double tol, int iters, int init,
+                     void* relres, void* bx, int32_t* its,
+                     double* coef, int64_t cap, double* rz0,
+                     void* work, int64_t work_bytes, void* stream)
+{
+	if (cap < 1) { set_error("stpy_pcg_lanczos: cap=%lld", (long long)cap); return -19; }
+	if (!coef || !rz0) { set_error("stpy_pcg_lanczos: null coef or rz0"); return -3; }
+	return pcg_checked("stpy_pcg_lanczos", kind, dtype, x, n, ldx, d, cols, inv_ls, kappa, diag_add, Gt, ldgt, Gn, ldgn, r, Bt, ldb, Xt, ldxt, t, tol, iters, init,
+	                   relres, bx, its, work, work_bytes, stream, PcgRec{coef, cap, rz0});
 }
 
 }  // extern "C"
