@@ -520,6 +520,33 @@ int stpy_kmv_dtheta(int kind, int dtype, const void* x, int64_t n, int64_t ldx, 
                     void* out, int64_t ldo, void* work, int64_t work_bytes, void* stream);
 
 /*
+ * Values and query-point gradients of kernel sums, the kernel matrix never formed: n query points a (n x lda), q contracted points b (q x ldb) and
+ * t coefficient rows Vt (t x q, ldv >= q).  With e_ijk = (a_i - b_j)[cols[k]] * inv_ls[k] (difference first, scale second), rho_ij = sum_k e_ijk^2
+ * (fma, in coordinate order), phi and chi = 2 dphi/drho as for stpy_kmv_dtheta:
+ *   out[c*ldc + i*ldo + k] = inv_ls[k] * sum_j Vt[c,j] kappa chi(rho_ij) e_ijk        k < d     (d / d a_i[cols[k]] of the next line)
+ *   out[c*ldc + i*ldo + d] =             sum_j Vt[c,j] kappa phi(rho_ij)                         (the value stpy_kmv returns, the same kernel bits)
+ * ldo >= d + 1 is the stride between query points and ldc >= n * ldo the stride between coefficient rows, both in elements: any (t, n, d + 1)
+ * window with a unit last stride.  Gradient columns are compact, in the order of cols (the caller scatters them).  A pair with rho == 0 contributes exactly 0 to the first d outputs
+ * (no 0 / 0 for MATERN12).  kind, cols, inv_ls, kappa as for stpy_kmv.  Vt = alpha^T gives the posterior mean and its input gradient; the rows of a
+ * pathwise-conditioning solve give the data term of t posterior draws.
+ * The launch shape of stpy_kmv_dtheta: a workgroup owns 64 query points and 16 rows c and walks j in a fixed order; on the 16x16x4 MFMA a lane
+ * evaluates rho, phi, chi and the d differences of the one pair (i, j) its B operand wants and issues d + 1 matrix instructions against the same
+ * fragment of Vt.  Coordinates stay in registers up to d = 16 (instantiations for 4, 8, 16); beyond, a workgroup owns the columns of one group of 8
+ * coordinates.  The D tile is stored per query point (no reduction over i).  With too few workgroups to fill the chip the j range is cut into
+ * pieces whose tiles pass through `work` and are added in piece order by a second launch: no atomics, no spin-waits, no cooperative grid.  Two
+ * calls give the same bits, and lda / ldb / ldv / ldc / ldo do not change a bit.  At most two launches, no host synchronisation, no allocation.
+ * Refused before any HIP call: kind (-1), dtype (-2), NULL a / inv_ls / out, or NULL b / Vt with q > 0 (-3), n or q negative or >= 2^31 (-4), lda or
+ * ldb < d (-5), d < 1 (-6), t < 1 or more than 65535 blocks of 16 rows x coordinate groups (-10), kappa not finite (-11), ldv < q (-13), work not
+ * 8-byte aligned (-17), work NULL or work_bytes below stpy_kmv_dx_workspace_bytes(dtype, n, q, d, t) (-20), ldo < d + 1 (-22), ldc < n * ldo (-23).
+ * n == 0: returns 0, nothing is written (no pointer is looked at).  q == 0: out[c, i, 0 .. d] = 0.
+ */
+int64_t stpy_kmv_dx_workspace_bytes(int dtype, int64_t n, int64_t q, int d, int64_t t);
+int stpy_kmv_dx(int kind, int dtype, const void* a, int64_t n, int64_t lda, const void* b, int64_t q, int64_t ldb,
+                int d, const int32_t* cols, const void* inv_ls, double kappa,
+                const void* Vt, int64_t ldv, int64_t t,
+                void* out, int64_t ldc, int64_t ldo, void* work, int64_t work_bytes, void* stream);
+
+/*
  * Input gradients of the GP posterior (gauss_procc.py:420-459 mean_gradient_hessian / gradient_mean_var and the
  * autograd of mean_std through a test tensor with requires_grad; ucb_optimize, :918-963).  One kernel term k = kappa phi,
  * test points xt (m x ldt) against training points x (n x ldx), scaled differences e = (xt - x_i)[cols] * inv_ls:

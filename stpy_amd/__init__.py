@@ -16,7 +16,7 @@ from .kernels import KernelFunction
 from .continuous_processes.gauss_procc import GaussianProcess
 from .embeddings.embedding import Embedding, RFFEmbedding, QuadratureEmbedding, HermiteEmbedding
 from .continuous_processes.nystrom_fea import NystromFeatures, pivoted_cholesky
-from .continuous_processes.iterative_gp import IterativeGaussianProcess
+from .continuous_processes.iterative_gp import IterativeGaussianProcess, PathwiseSamples
 
 __all__ = ["KernelFunction", "GaussianProcess", "Embedding", "RFFEmbedding", "QuadratureEmbedding", "HermiteEmbedding", "NystromFeatures", "pivoted_cholesky",
-		   "IterativeGaussianProcess"]
+		   "IterativeGaussianProcess", "PathwiseSamples"]

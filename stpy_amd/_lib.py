@@ -79,6 +79,8 @@ SIGNATURES = {
 								_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_kmv_dtheta_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_kmv_dtheta": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+	"stpy_kmv_dx_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i64]),
+	"stpy_kmv_dx": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
 	"stpy_gram_grad_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i32]),
 	"stpy_gram_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_trsm_ln_factor": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
@@ -521,6 +523,25 @@ def kmv_dtheta(kind, x, inv_ls, Ut, Vt, out, cols=None, kappa=1.0, work=None):
 	work = kmv_dtheta_workspace(n, d, t, out) if work is None else work
 	_launch("stpy_kmv_dtheta", kind, dtype_code(out.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(inv_ls), float(kappa), ptr(Ut), ld(Ut), ptr(Vt), ld(Vt), t,
 			ptr(out), ld(out), ptr(work), work.numel())
+
+
+def kmv_dx_workspace(n, q, d, t, like):
+	"""Scratch of stpy_kmv_dx (the tiles of a cut j range); one buffer can serve several launches of the same shape."""
+	return _work(load().stpy_kmv_dx_workspace_bytes(dtype_code(like.dtype), n, q, d, t), like)
+
+
+def kmv_dx(kind, a, b, Vt, out, inv_ls, cols=None, kappa=1.0, work=None):
+	"""out[c, i] = (d/da_i[cols[k]] for k < d, then the value) of sum_j Vt[c, j] k(a_i, b_j), the kernel matrix never formed (stpy_kmv_dx in the
+	header).  Vt: (t, |b|), may be a column window of wider storage; out: (t, |a|, >= d + 1) with a unit last stride, may be a window of wider
+	storage in both leading dimensions."""
+	n, q, d, t = a.shape[0], b.shape[0], _ncols(a, cols), Vt.shape[0]
+	if out.dim() != 3 or out.shape[0] != t or out.shape[1] != n or out.shape[2] < d + 1 or out.stride(2) != 1:
+		raise StpyHipError("kmv_dx: out must be (t, n, >= d + 1) = (%d, %d, >= %d) with a unit last stride, got %s" % (t, n, d + 1, tuple(out.shape)))
+	ldo = out.stride(1) if n > 1 else max(out.stride(1), int(out.shape[2]))
+	ldc = out.stride(0) if t > 1 else max(out.stride(0), n * ldo)
+	work = kmv_dx_workspace(n, q, d, t, out) if work is None else work
+	_launch("stpy_kmv_dx", kind, dtype_code(out.dtype), ptr(a), n, ld(a), ptr(b), q, ld(b), d, ptr(cols), ptr(inv_ls), float(kappa),
+			ptr(Vt), ld(Vt), t, ptr(out), ldc, ldo, ptr(work), work.numel())
 
 
 def rff_embed(x, W, m, scale, bias=None, feat_scale=None, transposed=False, workspace=False):

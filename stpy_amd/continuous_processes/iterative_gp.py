@@ -16,8 +16,11 @@ holds problems whose factor it cannot.  The price: every solve is iterative, and
 Out of scope, each for its own reason (all raise NotImplementedError before the device is touched):
   log_marginal / optimize_params   the log-determinant of a matrix that is never formed needs stochastic Lanczos quadrature, an estimator with
                                    its own variance and probe count: a different contract from the exact evidence the other classes return;
-  sample                           a posterior draw needs a square root of the N x N posterior covariance (Lanczos or pathwise conditioning);
-  input gradients                  (a test tensor with requires_grad) the gradient of the variance needs K*' A^-1 k*, more solves per point;
+  sample                           the reference's ``sample`` promises a draw of the exact posterior at the test points, which needs a square root of the
+                                   N x N posterior covariance; the matrix-free draw lives in a finite Fourier basis of the prior and has its own
+                                   name, ``sample_paths`` (below), as the stochastic evidence has;
+  input gradients by autograd      (a test tensor with requires_grad) the gradient of the variance needs K*' A^-1 k*, more solves per point; the
+                                   gradient of the MEAN and of drawn paths is served by ``mean_value_grad`` and ``sample_paths`` (below);
   composite kernels                the operator is evaluated inside the kernel for ONE stationary term (SE / Matern / ARD), the terms the pivoted
                                    Cholesky preconditioner covers as well;
   Sigma                            a general noise matrix is a second dense N x N operand;
@@ -39,6 +42,21 @@ standard error, never returned where the exact evidence is asked for.
               stpy_kmv_dtheta: one pass over 1 + 2 t pairs and one over the r columns of G.  One evaluation with gradient = one stpy_pchol,
               one block solve of 1 + t columns, the derivative passes.  The standard error shrinks with 1 / sqrt(num_probes) and with the quality of the preconditioner: the
               probes only see what the rank-r factor leaves of K (large for a slowly decaying spectrum, e.g. Matern 5/2 at r << n).
+
+Choosing the next point, matrix-free (csrc/kmvdx.hip, stpy_kmv_dx: values AND query-point gradients of sum_j V[c, j] k(x, x_j) for several rows c):
+
+  mean_value_grad   (mu, d mu / dx) at the test points: ONE stpy_kmv_dx with Vt = alpha^T.
+  sample_paths      pathwise conditioning (Matheron's rule): f_s(x) = phi(x)^T theta_s + k(x, X) v_s with v_s = A^-1 (y - Phi(X) theta_s - s eps_s),
+              theta_s ~ N(0, I), eps_s ~ N(0, I), phi a random-Fourier basis of the prior (m / 2 frequencies W_j = (z_j tau_j) o inv_ls; tau = 1 for
+              SE, sqrt(2 nu / u_j) with u_j ~ chi^2(2 nu) for Matern: the multivariate-t spectral density; cos and sin of the same frequency).
+              The residual rows are built in row slabs of X (stpy_rff_embed, stpy_gemm_nt: Phi(X) is never stored whole), then ONE block solve
+              per ``rhs_block`` draws.  The draw is exact GIVEN the basis -- its mean is the posterior mean and its variance the posterior
+              variance of the model whose prior is the m-feature expansion, observed with noise s -- and the basis is the only approximation.
+              The noise draw eps belongs to the rule: without it the variance of the draw is too small by s^2 |A^-1 k*|^2.
+              The returned ``PathwiseSamples`` is a deterministic function with an analytic gradient: data term by stpy_kmv_dx, prior term by
+              stpy_rff_grad, no further solve.
+  sample_and_optimize   batch Thompson sampling: ``size`` paths from one block solve, each climbed from ``multistart`` starts, all of them one
+              stacked L-BFGS-B problem with one batched device evaluation per step.
 """
 import numpy as np
 import scipy.linalg
@@ -75,6 +93,7 @@ class IterativeGaussianProcess(Estimator):
 		self.tol, self.maxiter, self.check_every, self.rhs_block = tol, int(maxiter), int(check_every), int(rhs_block)
 		self.num_probes, self.probe_seed = int(num_probes), int(probe_seed)
 		self.evidence_info = None
+		self.path_info = self.optimize_info = None
 		self._probes = None
 		self.trace_error = None
 		self.cg_info = {"iterations": 0, "relres": 0.0, "rank": 0, "kmv_launches": 0}
@@ -475,6 +494,214 @@ class IterativeGaussianProcess(Estimator):
 	def ucb(self, xtest):
 		mu, s = self.mean_std(xtest)
 		return mu + 2 * s
+
+	# ------------------------------------------------------------------ input gradients and pathwise samples
+	def mean_value_grad(self, xtest):
+		"""Posterior mean (M, 1) and its input gradient (M, d): ONE stpy_kmv_dx against alpha.  Not fitted: zeros (the prior mean)."""
+		self._no_grad(xtest)
+		xtest = torch.as_tensor(xtest)
+		m = xtest.shape[0]
+		if not self.fitted:
+			dt = xtest.dtype if xtest.dtype in (torch.float32, torch.float64) else torch.float64
+			return torch.zeros((m, 1), dtype=dt, device=xtest.device), torch.zeros((m, self.d), dtype=dt, device=xtest.device)
+		xd = self._xd
+		xt = _lib.to_device(xtest, xd.dtype)
+		t, cols, inv_ls = self._operands(xd)
+		dsel = inv_ls.numel()
+		out = torch.zeros((1, m, dsel + 1), dtype=xd.dtype, device=xd.device)
+		if m > 0:
+			_lib.kmv_dx(t['kind'], xt, xd, self._alpha.reshape(1, -1), out, inv_ls, cols=cols, kappa=t['kappa'])
+			self._kmv_launches += 1
+			self.cg_info["kmv_launches"] = self._kmv_launches
+		grad = out[0, :, :dsel]
+		if cols is not None:
+			full = torch.zeros((m, xd.shape[1]), dtype=xd.dtype, device=xd.device)
+			full[:, t['group']] = grad
+			grad = full
+		return _lib.like_input(out[0, :, dsel].reshape(-1, 1).clone(), xtest), _lib.like_input(grad.clone(), xtest)
+
+	_DRAW_KEYS = ("z", "u", "theta", "eps")
+
+	def _path_draws(self, term, size, m, n, draws, seed):
+		"""The standard normal (u: chi-square) draws of sample_paths as float64 CPU tensors, shapes checked: z (m / 2, coordinates of the term),
+		u (m / 2,) for a Matern term (else None), theta (size, m), eps (size, n).  Default: a CPU generator seeded by ``seed``, in this order."""
+		dsel, two_nu = len(term['group']), _TWO_NU.get(term['kind'])
+		shapes = {"z": (m // 2, dsel), "u": (m // 2,), "theta": (size, m), "eps": (size, n)}
+		given = {} if draws is None else dict(draws)
+		for key in given:
+			if key not in self._DRAW_KEYS:
+				raise ValueError("IterativeGaussianProcess.sample_paths: draws has the unknown entry %r (known: 'z', 'u', 'theta', 'eps')" % (key,))
+		gen = torch.Generator(device="cpu").manual_seed(int(seed))
+		out = {}
+		for key in self._DRAW_KEYS:
+			if key == "u" and two_nu is None:
+				if given.get("u") is not None:
+					raise ValueError("IterativeGaussianProcess.sample_paths: draws['u'] belongs to a Matern kernel; the squared exponential has no radial mixing")
+				out["u"] = None
+				continue
+			if given.get(key) is not None:
+				v = torch.as_tensor(given[key]).detach().to(device="cpu", dtype=torch.float64)
+				if tuple(v.shape) != shapes[key]:
+					raise ValueError("IterativeGaussianProcess.sample_paths: draws[%r] must have shape %s, got %s" % (key, shapes[key], tuple(v.shape)))
+				if key == "u" and not bool((v > 0).all()):
+					raise ValueError("IterativeGaussianProcess.sample_paths: draws['u'] must be positive (chi-square draws)")
+			elif key == "u":
+				v = (torch.randn((m // 2, two_nu), generator=gen, dtype=torch.float64) ** 2).sum(dim=1)
+			else:
+				v = torch.randn(shapes[key], generator=gen, dtype=torch.float64)
+			out[key] = v
+		return out
+
+	def sample_paths(self, size=1, num_features=2048, seed=0, draws=None):
+		"""``size`` posterior draws by pathwise conditioning, as a ``PathwiseSamples`` function object (the module docstring states the rule).
+		num_features: m, even; the prior basis has m / 2 frequencies.  draws: {'z', 'u', 'theta', 'eps'} standard normal (u: chi-square with 2 nu
+		degrees of freedom) arrays that replace the seeded ones, so that an oracle can share them.  One block solve per ``rhs_block`` draws;
+		memory O(size N + slab m).  ``self.path_info``: iterations, relres, kmv_launches, features."""
+		term = _stationary_term(self.kernel_object)
+		size, m = int(size), int(num_features)
+		if size < 1:
+			raise ValueError("IterativeGaussianProcess.sample_paths: size=%d must be at least 1" % size)
+		if m < 2 or m % 2:
+			raise ValueError("IterativeGaussianProcess.sample_paths: num_features=%d must be even and positive (cos and sin of every frequency)" % m)
+		if not self.fitted or self.x is None:
+			raise AttributeError("IterativeGaussianProcess.sample_paths needs a fitted object: call fit_gp first")
+		n = self.x.shape[0]
+		dr = self._path_draws(term, size, m, n, draws, seed)
+		xd = self._xd
+		dt, dev = xd.dtype, xd.device
+		_, cols, inv_ls = self._operands(xd)
+		# the basis: W_j = (z_j tau_j) o inv_ls on the term's columns, stacked twice (cos | sin of the same frequency)
+		tau = torch.ones((m // 2, 1), dtype=torch.float64) if dr["u"] is None else torch.sqrt(float(_TWO_NU[term['kind']]) / dr["u"]).reshape(-1, 1)
+		Wh = torch.zeros((m // 2, xd.shape[1]), dtype=torch.float64)
+		Wh[:, term['group']] = dr["z"] * tau * torch.as_tensor(np.asarray(term['inv_ls'], dtype=np.float64)).reshape(1, -1)
+		W = torch.cat([Wh, Wh], dim=0).to(device=dev, dtype=dt)
+		scale = float(np.sqrt(2.0 / m) * np.sqrt(float(term['kappa'])))
+		theta = dr["theta"].to(device=dev, dtype=dt)
+		# residual rows R = 1 y^T - s eps - theta Phi(X)^T, in row slabs of X
+		R = dr["eps"].to(device=dev, dtype=dt)
+		R.mul_(-float(self.s)).add_(_lib.to_device(self.y, dt).reshape(1, -1))
+		slab = max(64, min(n, (1 << 24) // m))
+		for i0 in range(0, n, slab):
+			Phi = _lib.rff_embed(xd[i0:i0 + slab], W, m, scale)
+			T = torch.empty((size, Phi.shape[0]), dtype=dt, device=dev)
+			_lib.gemm_nt(theta, Phi, T)
+			R[:, i0:i0 + slab] -= T
+		V = torch.empty((size, n), dtype=dt, device=dev)
+		launches, its_max, worst = self._kmv_launches, 0, 0.0
+		for b0 in range(0, size, self.rhs_block):
+			Xt, _, its, rel = self._solve(R[b0:b0 + self.rhs_block], "sample_paths")
+			V[b0:b0 + self.rhs_block] = Xt
+			its_max, worst = max(its_max, int(its.max())), max(worst, rel)
+		self.cg_info["kmv_launches"] = self._kmv_launches
+		self.path_info = {"iterations": its_max, "relres": worst, "kmv_launches": self._kmv_launches - launches, "features": m}
+		return PathwiseSamples(xd, term, cols, inv_ls, W, scale, theta, V, self.x)
+
+	def sample_and_optimize(self, size=1, multistart=25, bounds=None, num_features=2048, seed=0):
+		"""Batch Thompson sampling: ``size`` paths from one block solve (``sample_paths``), each maximised over the box ``bounds`` (default: the
+		bounding box of the training points) from ``multistart`` uniform starts.  All size * multistart points are ONE stacked L-BFGS-B problem with
+		one batched device evaluation per step (``_multistart_maximize`` of gauss_procc.py; the starts come from np.random as there).  Returns
+		(solutions (size, d), values (size,)): the best climbed start of every path, never below the path's value at any of its starts.  ``self.optimize_info``: starts, evaluations."""
+		from .gauss_procc import _draw_starts, _multistart_maximize
+		size, multistart = int(size), int(multistart)
+		if multistart < 1:
+			raise ValueError("IterativeGaussianProcess.sample_and_optimize: multistart=%d must be at least 1" % multistart)
+		paths = self.sample_paths(size=size, num_features=num_features, seed=seed)
+		xd = self._xd
+		d = xd.shape[1]
+		if bounds is None:
+			lo, hi = xd.min(dim=0)[0].double().cpu().numpy(), xd.max(dim=0)[0].double().cpu().numpy()
+			bounds = tuple((float(a), float(b)) for a, b in zip(lo, hi))
+		bounds = tuple((float(a), float(b)) for (a, b) in bounds)
+		if len(bounds) != d:
+			raise ValueError("IterativeGaussianProcess.sample_and_optimize: %d bounds for d=%d" % (len(bounds), d))
+		starts = _draw_starts(size * multistart, d, bounds)
+		which = torch.arange(size, device=xd.device).repeat_interleave(multistart)
+		evaluate = lambda xt: paths._value_grad_device(xt, which)
+		x0 = np.asarray(starts, dtype=np.float64)
+		v0 = evaluate(torch.from_numpy(x0).to(device=xd.device, dtype=xd.dtype))[0].double().cpu().numpy()
+		sol, vals, evals = _multistart_maximize(evaluate, starts, bounds, xd.device, xd.dtype)
+		keep = v0 > vals                                                   # the line search watches the SUM: a start its climb did not improve stays
+		sol[keep], vals[keep] = x0[keep], v0[keep]
+		sol, vals = sol.reshape(size, multistart, d), vals.reshape(size, multistart)
+		best = np.argmax(vals, axis=1)
+		self.optimize_info = {"starts": np.asarray(starts).reshape(size, multistart, d), "evaluations": evals + 1, "paths": paths}
+		pick = np.arange(size)
+		return (_lib.like_input(torch.from_numpy(sol[pick, best].copy()).to(device=xd.device, dtype=xd.dtype), self.x),
+				_lib.like_input(torch.from_numpy(vals[pick, best].copy()).to(device=xd.device, dtype=xd.dtype), self.x))
+
+
+_TWO_NU = {_lib.K_MATERN12: 1, _lib.K_MATERN32: 3, _lib.K_MATERN52: 5}          # degrees of freedom of the multivariate-t spectral density
+
+
+class PathwiseSamples:
+	"""``size`` posterior draws of an IterativeGaussianProcess as deterministic functions: f_s(x) = phi(x)^T theta_s + k(x, X) v_s.  Calling the
+	object returns the values (M, size); ``value_grad`` also the input gradients.  The data term is ONE stpy_kmv_dx against the rows v_s; the
+	prior term is stpy_rff_grad with per-point coefficient rows, added into the same result.  No solve, and no host synchronisation beyond
+	the result.  The object keeps what it needs (points, basis, theta, v) and does not change when the estimator is refitted."""
+
+	CHUNK = 256          # points per stpy_rff_grad launch, always this many (padded): a point's bits do not depend on how many points ride with it
+
+	def __init__(self, xd, term, cols, inv_ls, W, scale, theta, V, ref):
+		self._xd, self._term, self._cols, self._inv_ls = xd, term, cols, inv_ls
+		self._W, self._scale, self._theta, self._V, self._ref = W, scale, theta, V, ref
+		self.size, self.num_features, self.d = V.shape[0], W.shape[0], xd.shape[1]
+
+	def _value_grad_device(self, xt, which=None):
+		"""Device in, device out: (values, gradients) as (M, size), (M, size, d), or with which (M,) as (M,), (M, d)."""
+		xd, dsel, size, m, d = self._xd, self._inv_ls.numel(), self.size, self.num_features, self.d
+		dt, dev = xd.dtype, xd.device
+		M = xt.shape[0]
+		out = torch.zeros((size, M, dsel + 1), dtype=dt, device=dev)
+		if M > 0:
+			_lib.kmv_dx(self._term['kind'], xt, xd, self._V, out, self._inv_ls, cols=self._cols, kappa=self._term['kappa'])
+		if which is None:
+			data = out.permute(1, 0, 2).reshape(M * size, dsel + 1)          # stacked point p = i * size + s
+			pts = xt.repeat_interleave(size, dim=0)
+			idx = torch.arange(size, device=dev).repeat(M)
+		else:
+			idx = which.to(device=dev, dtype=torch.long)
+			data = out[idx, torch.arange(M, device=dev)]
+			pts = xt
+		S = pts.shape[0]
+		val = torch.empty((S,), dtype=dt, device=dev)
+		G = torch.empty((S, d), dtype=dt, device=dev)
+		group = self._term['group']
+		for p0 in range(0, S, self.CHUNK):
+			k = min(self.CHUNK, S - p0)
+			xc = torch.zeros((self.CHUNK, d), dtype=dt, device=dev)
+			xc[:k] = pts[p0:p0 + k]
+			C = torch.zeros((self.CHUNK, m), dtype=dt, device=dev)
+			C[:k] = self._theta[idx[p0:p0 + k]]
+			vc = torch.zeros((self.CHUNK,), dtype=dt, device=dev)
+			Gc = torch.zeros((self.CHUNK, d), dtype=dt, device=dev)
+			vc[:k] = data[p0:p0 + k, dsel]
+			Gc[:k, group] = data[p0:p0 + k, :dsel]
+			_lib.rff_grad(xc, self._W, m, self._scale, C, Gc, val=vc, combine=_lib.OUT_ADD)          # the prior term adds into the data term
+			val[p0:p0 + k] = vc[:k]
+			G[p0:p0 + k] = Gc[:k]
+		if which is None:
+			return val.reshape(M, size), G.reshape(M, size, d)
+		return val, G
+
+	def value_grad(self, xtest, which=None):
+		"""((M, size), (M, size, d)) values and input gradients of every path at every test point; with ``which`` (M,) integers, point i on path
+		which[i] only: ((M,), (M, d)), the matching entries of the full call bit for bit."""
+		if torch.is_tensor(xtest) and xtest.requires_grad:
+			raise NotImplementedError("PathwiseSamples.value_grad returns the analytic gradient itself: pass a test tensor without requires_grad")
+		xtest = torch.as_tensor(xtest)
+		if xtest.dim() != 2 or xtest.shape[1] != self.d:
+			raise ValueError("PathwiseSamples: test points must be (M, %d), got %s" % (self.d, tuple(xtest.shape)))
+		if which is not None:
+			which = torch.as_tensor(which)
+			if which.dim() != 1 or which.shape[0] != xtest.shape[0] or which.dtype.is_floating_point:
+				raise ValueError("PathwiseSamples.value_grad: which must be (M,) = (%d,) integers, got %s %s" % (xtest.shape[0], tuple(which.shape), which.dtype))
+			if which.numel() and (int(which.min()) < 0 or int(which.max()) >= self.size):
+				raise IndexError("PathwiseSamples.value_grad: which outside [0, %d)" % self.size)
+		val, G = self._value_grad_device(_lib.to_device(xtest, self._xd.dtype), which)
+		return _lib.like_input(val, xtest), _lib.like_input(G, xtest)
+
+	def __call__(self, xtest):
+		return self.value_grad(xtest)[0]
 
 
 def _control_variate(a, b, Eb):

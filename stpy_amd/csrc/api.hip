@@ -613,3 +613,6 @@ int stpy_profile_read_union(int tagmask, double* busy_ms, double* total_flops, i
 
 // stpy_kmv_dtheta and its workspace query: the matrix-free hyper-parameter derivative (kmvgrad.hip), compiled here for the same reason.
 #include "kmvgrad.hip"
+
+// stpy_kmv_dx and its workspace query: values and query-point gradients of matrix-free kernel sums (kmvdx.hip), compiled here for the same reason.
+#include "kmvdx.hip"
