@@ -547,6 +547,35 @@ int stpy_kmv_dx(int kind, int dtype, const void* a, int64_t n, int64_t lda, cons
                 void* out, int64_t ldc, int64_t ldo, void* work, int64_t work_bytes, void* stream);
 
 /*
+ * Values, query-point gradients and query-point Hessians of kernel sums, the kernel matrix never formed: stpy_kmv_dx with the second order added.
+ * a, b, Vt, kind, cols, inv_ls, kappa, e_ijk, rho_ij, phi and chi as for stpy_kmv_dx; psi = 2 dchi/drho (SE: exp(-rho / 2); MATERN52:
+ * (25 / 3) exp(-sqrt(5 rho))):
+ *   out[c*ldc + i*ldo + k]                    = inv_ls[k] * sum_j Vt[c,j] kappa chi e_ijk                                    k < d   (as stpy_kmv_dx)
+ *   out[c*ldc + i*ldo + d]                    =             sum_j Vt[c,j] kappa phi                                                   (as stpy_kmv_dx)
+ *   out[c*ldc + i*ldo + d + 1 + k(k+1)/2 + l] = inv_ls[k] inv_ls[l] * sum_j Vt[c,j] kappa (psi e_ijk e_ijl + chi [k == l])   l <= k < d
+ * the last block being d2 / d a_i[cols[k]] d a_i[cols[l]] of the value.  Only the lower triangle is stored, row by row, compact and in the order of
+ * cols (the caller scatters and mirrors).  ldo >= 1 + d + d (d + 1) / 2 is the stride between query points and ldc >= n * ldo the stride between
+ * coefficient rows, both in elements.  A pair with rho == 0 contributes exactly 0 to the gradient and kappa chi(0) [k == l] times the scales to the
+ * Hessian.  Kinds: SE and MATERN52 only (the second derivative of MATERN12 / MATERN32 is singular at r = 0).  d <= 16 selected coordinates.
+ * The launch shape of stpy_kmv_dx: a workgroup owns 64 query points, 16 rows c and ONE GROUP of output columns (the gradient and the value; or
+ * Hessian rows g - 1 and d - g, d + 1 columns together) and re-evaluates the pair per group; 1 + ceil(d / 2) groups.  With too few workgroups to
+ * fill the chip the j range is cut into pieces whose tiles pass through `work` and are added in piece order by a second launch: no atomics, no
+ * spin-waits, no cooperative grid.  Two calls give the same bits, and lda / ldb / ldv / ldc / ldo do not change a bit.  At most two launches, no
+ * host synchronisation, no allocation.
+ * Refused before any HIP call: kind other than SE / MATERN52 (-1), dtype (-2), NULL a / inv_ls / out, or NULL b / Vt with q > 0 (-3), n or q negative
+ * or >= 2^31 (-4), lda or ldb < d (-5), d < 1 or d > 16 (-6), t < 1 or more than 65535 blocks of 16 rows x column groups (-10), kappa not finite
+ * (-11), ldv < q (-13), work not 8-byte aligned (-17), work NULL or work_bytes below stpy_kmv_dxx_workspace_bytes(dtype, n, q, d, t) (-20),
+ * ldo < 1 + d + d (d + 1) / 2 (-22), ldc < n * ldo (-23).
+ * n == 0: returns 0, nothing is written (no pointer is looked at).  q == 0: every output of every point is 0.
+ * stpy_kmv_dxx_workspace_bytes does not decrease in n, q or t: a buffer sized for the largest problem of a run serves every smaller one.
+ */
+int64_t stpy_kmv_dxx_workspace_bytes(int dtype, int64_t n, int64_t q, int d, int64_t t);
+int stpy_kmv_dxx(int kind, int dtype, const void* a, int64_t n, int64_t lda, const void* b, int64_t q, int64_t ldb,
+                 int d, const int32_t* cols, const void* inv_ls, double kappa,
+                 const void* Vt, int64_t ldv, int64_t t,
+                 void* out, int64_t ldc, int64_t ldo, void* work, int64_t work_bytes, void* stream);
+
+/*
  * Input gradients of the GP posterior (gauss_procc.py:420-459 mean_gradient_hessian / gradient_mean_var and the
  * autograd of mean_std through a test tensor with requires_grad; ucb_optimize, :918-963).  One kernel term k = kappa phi,
  * test points xt (m x ldt) against training points x (n x ldx), scaled differences e = (xt - x_i)[cols] * inv_ls:

@@ -81,6 +81,8 @@ SIGNATURES = {
 	"stpy_kmv_dtheta": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
 	"stpy_kmv_dx_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i64]),
 	"stpy_kmv_dx": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+	"stpy_kmv_dxx_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i64]),
+	"stpy_kmv_dxx": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
 	"stpy_gram_grad_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i32]),
 	"stpy_gram_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _dbl, _vp, _vp, _vp, _i64, _vp, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp]),
 	"stpy_trsm_ln_factor": (_i32, [_i32, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
@@ -541,6 +543,32 @@ def kmv_dx(kind, a, b, Vt, out, inv_ls, cols=None, kappa=1.0, work=None):
 	ldc = out.stride(0) if t > 1 else max(out.stride(0), n * ldo)
 	work = kmv_dx_workspace(n, q, d, t, out) if work is None else work
 	_launch("stpy_kmv_dx", kind, dtype_code(out.dtype), ptr(a), n, ld(a), ptr(b), q, ld(b), d, ptr(cols), ptr(inv_ls), float(kappa),
+			ptr(Vt), ld(Vt), t, ptr(out), ldc, ldo, ptr(work), work.numel())
+
+
+def kmv_dxx_ncol(d):
+	"""Columns of a point in the output of stpy_kmv_dxx: d gradients, the value, the lower triangle of the Hessian row by row."""
+	return 1 + d + d * (d + 1) // 2
+
+
+def kmv_dxx_workspace(n, q, d, t, like):
+	"""Scratch of stpy_kmv_dxx (the tiles of a cut j range); does not decrease in n, q or t, so one buffer sized for the largest problem serves all."""
+	return _work(load().stpy_kmv_dxx_workspace_bytes(dtype_code(like.dtype), n, q, d, t), like)
+
+
+def kmv_dxx(kind, a, b, Vt, out, inv_ls, cols=None, kappa=1.0, work=None):
+	"""out[c, i] = (d/da_i[cols[k]] for k < d, the value, then d2/da_i[cols[k]] da_i[cols[l]] for l <= k < d at d + 1 + k (k + 1) / 2 + l) of
+	sum_j Vt[c, j] k(a_i, b_j), the kernel matrix never formed (stpy_kmv_dxx in the header; SE and Matern 5/2, d <= 16).  Vt: (t, |b|), may be a
+	column window of wider storage; out: (t, |a|, >= 1 + d + d (d + 1) / 2) with a unit last stride, may be a window of wider storage in both
+	leading dimensions."""
+	n, q, d, t = a.shape[0], b.shape[0], _ncols(a, cols), Vt.shape[0]
+	nc = kmv_dxx_ncol(d)
+	if out.dim() != 3 or out.shape[0] != t or out.shape[1] != n or out.shape[2] < nc or out.stride(2) != 1:
+		raise StpyHipError("kmv_dxx: out must be (t, n, >= 1 + d + d (d + 1) / 2) = (%d, %d, >= %d) with a unit last stride, got %s" % (t, n, nc, tuple(out.shape)))
+	ldo = out.stride(1) if n > 1 else max(out.stride(1), int(out.shape[2]))
+	ldc = out.stride(0) if t > 1 else max(out.stride(0), n * ldo)
+	work = kmv_dxx_workspace(n, q, d, t, out) if work is None else work
+	_launch("stpy_kmv_dxx", kind, dtype_code(out.dtype), ptr(a), n, ld(a), ptr(b), q, ld(b), d, ptr(cols), ptr(inv_ls), float(kappa),
 			ptr(Vt), ld(Vt), t, ptr(out), ldc, ldo, ptr(work), work.numel())
 
 

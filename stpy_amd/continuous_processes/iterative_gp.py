@@ -13,14 +13,18 @@ holds problems whose factor it cannot.  The price: every solve is iterative, and
   mean_std    the mean as above; the variance by BLOCK SOLVES, one stpy_pcg solve per ``rhs_block`` test points, each as expensive as the fit
               (t columns share every kernel evaluation, so a block costs about one fit, not rhs_block fits).  sigma = sqrt(kdiag - <k*, A^-1 k*>).
 
-Out of scope, each for its own reason (all raise NotImplementedError before the device is touched):
+Out of scope, each for its own reason (what has an entry point raises NotImplementedError before the device is touched):
   log_marginal / optimize_params   the log-determinant of a matrix that is never formed needs stochastic Lanczos quadrature, an estimator with
                                    its own variance and probe count: a different contract from the exact evidence the other classes return;
   sample                           the reference's ``sample`` promises a draw of the exact posterior at the test points, which needs a square root of the
                                    N x N posterior covariance; the matrix-free draw lives in a finite Fourier basis of the prior and has its own
                                    name, ``sample_paths`` (below), as the stochastic evidence has;
-  input gradients by autograd      (a test tensor with requires_grad) the gradient of the variance needs K*' A^-1 k*, more solves per point; the
-                                   gradient of the MEAN and of drawn paths is served by ``mean_value_grad`` and ``sample_paths`` (below);
+  input gradients by autograd      (a test tensor with requires_grad) the analytic gradients have methods of their own, which return them
+                                   directly: ``mean_std_grad`` (mean AND standard deviation; no solve beyond the one ``mean_std`` makes),
+                                   ``mean_value_grad``, ``mean_value_grad_hessian`` and ``sample_paths`` (below);
+  Hessians of pathwise samples     the prior term's second derivative (random features) has no kernel; the MEAN's Hessian is served (below);
+  warm-started solves              between the L-BFGS steps of ``ucb_optimize`` every block solve starts from zero: stpy_pcg has no initial guess;
+  Hessians beyond d = 16           stpy_kmv_dxx holds the selected coordinates in registers: at most 16 of them;
   composite kernels                the operator is evaluated inside the kernel for ONE stationary term (SE / Matern / ARD), the terms the pivoted
                                    Cholesky preconditioner covers as well;
   Sigma                            a general noise matrix is a second dense N x N operand;
@@ -57,6 +61,18 @@ Choosing the next point, matrix-free (csrc/kmvdx.hip, stpy_kmv_dx: values AND qu
               stpy_rff_grad, no further solve.
   sample_and_optimize   batch Thompson sampling: ``size`` paths from one block solve, each climbed from ``multistart`` starts, all of them one
               stacked L-BFGS-B problem with one batched device evaluation per step.
+
+The deterministic acquisition, matrix-free.  With w = A^-1 k*(x) -- exactly the row of the block solve that ``mean_std`` makes for its variance --
+    var(x) = k(x, x) - k*(x)^T w,     grad var(x) = grad k(x, x) - 2 sum_j w_j grad_x k(x, x_j)
+(A^-1 is symmetric: both factors of the quadratic form give the same term), grad std = grad var / (2 std), 0 where std = 0.  No further solve:
+
+  mean_std_grad     (d mu, d std), each (M, d): per ``rhs_block`` test points the block solve of ``mean_std``, its rows KEPT; d mu by stpy_kmv_dx, d std by
+              the paired-weight form of stpy_gram_grad (KernelFunction._grad_into with Wt = the solve's rows, v = -1 / std) -- milliseconds
+              beside the solve.  Memory O(M N) for the kept rows.
+  ucb_optimize      GaussianProcess.ucb_optimize on this posterior: all starts one stacked L-BFGS-B problem, every evaluation
+              ceil(multistart / rhs_block) block solves (each about one fit).
+  mean_value_grad_hessian / mean_gradient_hessian   the mean, its input gradient and its input Hessian: ONE stpy_kmv_dxx (csrc/kmvdxx.hip) against
+              alpha.  SE and Matern 5/2 (the second derivative of Matern 1/2 and 3/2 is singular at r = 0), at most 16 selected coordinates.
 """
 import numpy as np
 import scipy.linalg
@@ -77,8 +93,9 @@ _OUT_OF_SCOPE = {
 class IterativeGaussianProcess(Estimator):
 
 	def __init__(self, gamma=1, s=0.001, kappa=1., kernel_name="squared_exponential", d=1, kernel=None,
-				 precond_rank=256, precond_tol=0., tol=None, maxiter=1000, check_every=10, rhs_block=64, nu=1.5, num_probes=16, probe_seed=0):
+				 precond_rank=256, precond_tol=0., tol=None, maxiter=1000, check_every=10, rhs_block=64, nu=1.5, num_probes=16, probe_seed=0, bounds=None):
 		self.s = s
+		self.bounds = bounds
 		self.d = d
 		self.x = self.y = None
 		self.n = 0
@@ -99,6 +116,7 @@ class IterativeGaussianProcess(Estimator):
 		self.cg_info = {"iterations": 0, "relres": 0.0, "rank": 0, "kmv_launches": 0}
 		self._xd = self._alpha = self._Gt = self._Gn = None
 		self._kmv_launches = 0
+		self._solves = 0                                                  # block solves of the posterior variance (mean_std, mean_std_grad, ucb_optimize)
 		self._check()
 
 	def _check(self):
@@ -132,8 +150,8 @@ class IterativeGaussianProcess(Estimator):
 	@staticmethod
 	def _no_grad(xtest):
 		if torch.is_tensor(xtest) and xtest.requires_grad:
-			raise NotImplementedError("IterativeGaussianProcess has no input gradients (the variance's gradient needs further solves per test point): "
-									  "pass a test tensor without requires_grad")
+			raise NotImplementedError("IterativeGaussianProcess returns its analytic input gradients directly (mean_std_grad, mean_value_grad, "
+									  "mean_value_grad_hessian) instead of through autograd: pass a test tensor without requires_grad")
 
 	# ------------------------------------------------------------------ the solver
 	def _operands(self, xd):
@@ -466,24 +484,33 @@ class IterativeGaussianProcess(Estimator):
 		self._no_grad(xtest)
 		if not self.fitted:
 			return self._prior(xtest)
+		mu, sigma, _ = self._mean_std_device(_lib.to_device(xtest, self._xd.dtype), "mean_std")
+		return _lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(sigma.reshape(-1, 1), xtest)
+
+	def _mean_std_device(self, xt, what, keep=False):
+		"""mu, sigma (M,) for device test points and, with ``keep``, the rows w_i = A^-1 k*_i of the block solves as Wt (M, N) (else None): what the
+		variance's input gradient is made of, computed anyway and otherwise dropped."""
 		xd = self._xd
-		xt = _lib.to_device(xtest, xd.dtype)
 		m = xt.shape[0]
 		mu = self._mean_device(xt)
 		kd = torch.empty((m,), dtype=xd.dtype, device=xd.device)
 		self.kernel_object._diag_into(xt, kd)
 		bx = torch.empty((m,), dtype=xd.dtype, device=xd.device)
+		Wt = torch.empty((m, xd.shape[0]), dtype=xd.dtype, device=xd.device) if keep else None
 		for i0 in range(0, m, self.rhs_block):
 			chunk = xt[i0:i0 + self.rhs_block]
 			Bt = torch.empty((chunk.shape[0], xd.shape[0]), dtype=xd.dtype, device=xd.device)
 			self.kernel_object._kernel_into(xd, chunk, Bt)                  # rows k(x, xt_i): the right-hand sides, no transpose
-			_, b, _, _ = self._solve(Bt, "mean_std")
+			Xt, b, _, _ = self._solve(Bt, what)
 			bx[i0:i0 + chunk.shape[0]] = b
+			if keep:
+				Wt[i0:i0 + chunk.shape[0]] = Xt
+			self._solves += 1
 		self.cg_info["kmv_launches"] = self._kmv_launches
 		sigma = torch.empty((m,), dtype=xd.dtype, device=xd.device)
 		if m > 0:
 			_lib.predict_finish(sumsq=bx, kdiag=kd, scale=1.0, sigma=sigma)
-		return _lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(sigma.reshape(-1, 1), xtest)
+		return mu, sigma, Wt
 
 	mean_var = mean_std
 
@@ -494,6 +521,163 @@ class IterativeGaussianProcess(Estimator):
 	def ucb(self, xtest):
 		mu, s = self.mean_std(xtest)
 		return mu + 2 * s
+
+	# ------------------------------------------------------------------ input gradients of the posterior, Hessian of the mean
+	def _posterior(self, xtest):
+		"""mu, sigma (M,) on the device and what their input gradient needs: (xt, Wt or None, sigma), Wt (M, N) the kept rows A^-1 k*_i (the shapes of
+		GaussianProcess._posterior).  Costs ceil(M / rhs_block) block solves."""
+		if not self.fitted:
+			xt = _lib.to_device(xtest)
+			kd = torch.empty((xt.shape[0],), dtype=xt.dtype, device=xt.device)
+			self.kernel_object._diag_into(xt, kd)
+			sigma = torch.empty_like(kd)
+			_lib.predict_finish(sumsq=torch.zeros_like(kd), kdiag=kd, scale=0.0, sigma=sigma)
+			return torch.zeros_like(kd), sigma, (xt, None, sigma)
+		xt = _lib.to_device(xtest, self._xd.dtype)
+		mu, sigma, Wt = self._mean_std_device(xt, "mean_std_grad", keep=True)
+		return mu, sigma, (xt, Wt, sigma)
+
+	def _posterior_grad(self, state, gmu, gstd):
+		"""sum_t gmu_t grad mu(xt_t) + gstd_t grad sigma(xt_t), one row per test point: (M, d) on the device, no solve.  grad mu: one stpy_kmv_dx
+		against alpha.  grad sigma = (grad_x k(x, x) - 2 sum_j w_j grad_x k(x, x_j)) / (2 sigma), 0 where sigma is 0: the paired-weight
+		stpy_gram_grad with the kept rows w and v = -gstd / sigma, plus KernelFunction._self_grad_into (zero for the stationary terms served here)."""
+		xt, Wt, sigma = state
+		ko = self.kernel_object
+		G = torch.zeros(xt.shape, dtype=xt.dtype, device=xt.device)
+		m = xt.shape[0]
+		if m == 0:
+			return G
+		u = None if gmu is None else _lib.to_device(gmu, xt.dtype).reshape(-1)
+		gs = None if gstd is None else _lib.to_device(gstd, xt.dtype).reshape(-1)
+		if gs is not None and not bool((gs != 0).any()):
+			gs = None
+		if Wt is not None and u is not None:
+			t, cols, inv_ls = self._operands(self._xd)
+			dsel = inv_ls.numel()
+			out = torch.empty((1, m, dsel + 1), dtype=xt.dtype, device=xt.device)
+			_lib.kmv_dx(t['kind'], xt, self._xd, self._alpha.reshape(1, -1), out, inv_ls, cols=cols, kappa=t['kappa'])
+			self._kmv_launches += 1
+			self.cg_info["kmv_launches"] = self._kmv_launches
+			G[:, t['group']] = u.reshape(-1, 1) * out[0, :, :dsel]
+		if gs is not None:
+			pos = sigma > 0
+			safe = torch.where(pos, sigma, torch.ones_like(sigma))
+			if Wt is not None:
+				v = torch.where(pos, -gs / safe, torch.zeros_like(gs)).contiguous()
+				Gs = torch.zeros_like(G)
+				ko._grad_into(self._xd, xt, Gs, Wt=Wt, v=v)
+				G += Gs
+			ko._self_grad_into(xt, torch.where(pos, gs / (2.0 * safe), torch.zeros_like(gs)), G)
+		return G
+
+	def mean_std_grad(self, xtest):
+		"""Batched input gradients of the posterior: (d mu, d std), each (M, d), where the inputs live (GaussianProcess.mean_std_grad).  Cost: the
+		block solves of ``mean_std`` on the same points -- the rows w_i = A^-1 k*_i they produce ARE the coefficients of the variance's gradient --
+		and two cheap passes over the points.  Not fitted: zeros (the prior of a stationary kernel is flat)."""
+		xtest = torch.as_tensor(xtest).detach()
+		m = xtest.shape[0]
+		if not self.fitted:
+			dt = xtest.dtype if xtest.dtype in (torch.float32, torch.float64) else torch.float64
+			return torch.zeros((m, self.d), dtype=dt, device=xtest.device), torch.zeros((m, self.d), dtype=dt, device=xtest.device)
+		mu, sigma, state = self._posterior(xtest)
+		ones = torch.ones_like(sigma)
+		dmu = self._posterior_grad(state, ones, None)
+		dstd = self._posterior_grad(state, None, ones)
+		return _lib.like_input(dmu, xtest), _lib.like_input(dstd, xtest)
+
+	def ucb_optimize(self, beta, multistart=25, lcb=False):
+		"""GaussianProcess.ucb_optimize, matrix-free: maximise mu + sqrt(beta) sigma (mu - sqrt(beta) sigma with ``lcb``) over ``self.bounds`` from
+		``multistart`` uniform starts drawn with the reference's np.random calls in its order.  All starts are ONE stacked L-BFGS-B problem
+		(``_multistart_maximize`` of gauss_procc.py); every evaluation is ceil(multistart / rhs_block) block solves, each about the cost of the
+		fit, and the analytic gradients come out of the same solves.  Returns (solution (d,), value) of the best start, never below the
+		acquisition at any drawn start.  ``self.optimize_info``: starts, start_values, evaluations, solves (= evaluations * ceil(multistart / rhs_block)),
+		kmv_launches."""
+		from .gauss_procc import _draw_starts, _multistart_maximize
+		if self.bounds is None:
+			raise ValueError("ucb_optimize needs box bounds: set IterativeGaussianProcess.bounds to a list of (low, high) per coordinate")
+		multistart = int(multistart)
+		if multistart < 1:
+			raise ValueError("IterativeGaussianProcess.ucb_optimize: multistart=%d must be at least 1" % multistart)
+		bounds = tuple((float(a), float(b)) for (a, b) in self.bounds)
+		if len(bounds) != self.d:
+			raise ValueError("IterativeGaussianProcess.ucb_optimize: %d bounds for d=%d" % (len(bounds), self.d))
+		starts = _draw_starts(multistart, self.d, bounds)
+		sign, sb = (-1.0 if lcb else 1.0), float(np.sqrt(beta))
+		dev = self._xd.device if self._xd is not None else _lib.device()
+		dtype = self._xd.dtype if self._xd is not None else torch.float64
+		solves, launches = self._solves, self._kmv_launches
+		first = []
+
+		def value(xt):
+			mu, sigma, state = self._posterior(xt)
+			val = mu + sign * sb * sigma
+			if not first:
+				first.append(val.double().cpu().numpy())                    # the first evaluation is at the drawn starts
+			return val, state
+
+		def evaluate(xt):
+			val, state = value(xt)
+			return val, self._posterior_grad(state, torch.ones_like(val), torch.full_like(val, sign * sb))
+
+		sol, vals, evals = _multistart_maximize(evaluate, starts, bounds, dev, dtype, final=lambda xt: value(xt)[0])
+		x0, v0 = np.asarray(starts, dtype=np.float64), first[0]
+		keep = v0 > vals                                                   # the line search watches the SUM: a start its climb did not improve stays
+		sol[keep], vals[keep] = x0[keep], v0[keep]
+		index = int(np.argmax(vals))
+		self.optimize_info = {"starts": x0, "start_values": v0, "evaluations": evals, "solves": self._solves - solves,
+							  "kmv_launches": self._kmv_launches - launches}
+		return (torch.from_numpy(sol[index].copy()), torch.tensor(float(vals[index]), dtype=torch.float64))
+
+	def _hessian_refusal(self):
+		"""The dense class's refusal (KernelFunction._grad_into), on the host."""
+		t = _stationary_term(self.kernel_object)
+		if t['kind'] in (_lib.K_MATERN12, _lib.K_MATERN32):
+			raise NotImplementedError("Hessian of the %s term is not defined (singular at r = 0)" % self.kernel_object._term_name(t))
+		if len(t['group']) > 16:
+			raise NotImplementedError("IterativeGaussianProcess: the matrix-free Hessian (stpy_kmv_dxx) serves at most 16 selected coordinates, the kernel reads %d"
+									  % len(t['group']))
+		return t
+
+	def mean_value_grad_hessian(self, xtest):
+		"""Posterior mean (M, 1), its input gradient (M, d) and its input Hessian (M, d, d), symmetric and scattered to the full d (zero on the
+		coordinates the kernel does not read): ONE stpy_kmv_dxx against alpha.  Not fitted: zeros.  SE and Matern 5/2, at most 16 selected coordinates."""
+		self._no_grad(xtest)
+		self._hessian_refusal()
+		xtest = torch.as_tensor(xtest)
+		m = xtest.shape[0]
+		if not self.fitted:
+			dt = xtest.dtype if xtest.dtype in (torch.float32, torch.float64) else torch.float64
+			z = lambda *shape: torch.zeros(shape, dtype=dt, device=xtest.device)
+			return z(m, 1), z(m, self.d), z(m, self.d, self.d)
+		xd = self._xd
+		xt = _lib.to_device(xtest, xd.dtype)
+		t, cols, inv_ls = self._operands(xd)
+		dsel, width = inv_ls.numel(), xd.shape[1]
+		out = torch.zeros((1, m, _lib.kmv_dxx_ncol(dsel)), dtype=xd.dtype, device=xd.device)
+		if m > 0:
+			_lib.kmv_dxx(t['kind'], xt, xd, self._alpha.reshape(1, -1), out, inv_ls, cols=cols, kappa=t['kappa'])
+			self._kmv_launches += 1
+			self.cg_info["kmv_launches"] = self._kmv_launches
+		group = torch.as_tensor(t['group'], dtype=torch.long, device=xd.device)
+		grad = torch.zeros((m, width), dtype=xd.dtype, device=xd.device)
+		grad[:, group] = out[0, :, :dsel]
+		# the lower triangle, row by row, to both halves of the full matrix: the two copies of an entry are the same bits
+		rows, colsl = torch.tril_indices(dsel, dsel, device=xd.device)
+		H = torch.zeros((m, width, width), dtype=xd.dtype, device=xd.device)
+		tri = out[0, :, dsel + 1:]
+		H[:, group[rows], group[colsl]] = tri
+		H[:, group[colsl], group[rows]] = tri
+		return _lib.like_input(out[0, :, dsel].reshape(-1, 1).clone(), xtest), _lib.like_input(grad, xtest), _lib.like_input(H, xtest)
+
+	def mean_gradient_hessian(self, xtest, hessian=False):
+		"""The reference's convention (GaussianProcess.mean_gradient_hessian): the gradient (d,) of the posterior mean at the FIRST row of xtest,
+		and with ``hessian`` [gradient, Hessian (d, d)].  One stpy_kmv_dxx launch against alpha (one stpy_kmv_dx without the Hessian)."""
+		self._no_grad(xtest)
+		x1 = xtest[:1].detach() if torch.is_tensor(xtest) else torch.as_tensor(xtest[:1])
+		if hessian:
+			_, g, H = self.mean_value_grad_hessian(x1)
+			return [g[0], H[0]]
+		return self.mean_value_grad(x1)[1][0]
 
 	# ------------------------------------------------------------------ input gradients and pathwise samples
 	def mean_value_grad(self, xtest):

@@ -616,3 +616,6 @@ int stpy_profile_read_union(int tagmask, double* busy_ms, double* total_flops, i
 
 // stpy_kmv_dx and its workspace query: values and query-point gradients of matrix-free kernel sums (kmvdx.hip), compiled here for the same reason.
 #include "kmvdx.hip"
+
+// stpy_kmv_dxx and its workspace query: values, query-point gradients and Hessians of matrix-free kernel sums (kmvdxx.hip), compiled here for the same reason.
+#include "kmvdxx.hip"
