@@ -42,6 +42,9 @@ inline int potrf_auto_nb(int64_t n) { return n <= g_potrf_nb256_upto ? 256 : (n 
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// neither infinite nor NaN (a value known to be positive: !(v <= F64_MAX) alone; F64_MAX is constexpr, so kernels may name it too)
+constexpr double F64_MAX = 1.79769313486231570e308;
+inline bool is_finite(double v) { return v >= -F64_MAX && v <= F64_MAX; }
 
 // ---- look-ahead side stream (highest priority) + events used by potrf and the block solves.  One set per
 // ---- (device, caller stream), created on first use and kept for the life of the process: two host threads that

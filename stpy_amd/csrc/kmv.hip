@@ -1,67 +1,25 @@
 // Matrix-free products and solves with a kernel matrix generated on the fly: stpy_kmv, Yt = Vt (K + diag_add I) for a block of right-hand
 // sides stored one per row, and stpy_pcg, block preconditioned conjugate gradients on that operator.  K is never formed.
 //
-// stpy_kmv.  A workgroup of four waves owns 64 output points, 16 per wave, and walks the contracted points j in chunks of 64 in a fixed order.
-// The product runs on the 16x16x4 MFMA with A = a fragment of Vt (row = right-hand side, k = j) and B = a 4 x 16 fragment of K, whose operand
-// map wants ONE element per lane, B[k = lane >> 4][lane & 15]: lane l evaluates k(a_{i0 + (l & 15)}, b_{j0 + 4 s + (l >> 4)}) itself, from direct
-// coordinate differences with the evaluator of the pivoted Cholesky (pc_phi: the same bits, so the operator is the one the preconditioner's
-// factor was built from, bitwise symmetric when a == b, exactly kappa on coincident points), and feeds it straight in: kernel values pass
-// through neither LDS nor a shuffle.  D has col = lane & 15 = i, so rows of Yt are written in runs of 16 neighbouring elements.  The chunk of b
-// and the Vt block go through LDS; the a coordinates stay in registers up to d = 16 (instantiations for 4, 8 and 16) and go through LDS, 16
-// coordinates at a time, beyond.  The register forms evaluate a chunk in four rounds of four values per lane, which keeps the fp64 kernels at
-// 93 / 111 / 159 VGPRs (four, four and three waves per SIMD): with one wave per SIMD the load -> LDS -> barrier of every chunk was exposed and the
-// kernel ran 3.8 times slower.
-// Up to 64 right-hand sides (four accumulator tuples, ragged blocks zero-filled) share one kernel evaluation; blockIdx.z walks further 64s.
-// When the output tiles are too few to fill the chip the j range is cut into blockIdx.y pieces whose partial sums land in `work` and are
-// added in piece order by a second launch (the stpy_gram_grad pattern): no atomics, no spin-waits, no cooperative grid, no scratch, and the
-// same bits on every call and for every ldv / ldy.
-// The accumulators are C = D chains on four disjoint, fully live tuples (never two constant-C fp64 MFMAs on overlapping tuples: potrf.hip).
+// stpy_kmv is the plain pair walker of kmv_pair.h (the design, the cut and the fp64 rule are stated there) with the widest row block: up to 64
+// right-hand sides (four accumulator tuples, ragged blocks zero-filled) share one kernel evaluation, and blockIdx.z walks further 64s.  The
+// values are those of the pivoted Cholesky (pc_phi: the operator is the one the preconditioner's factor was built from, bitwise symmetric
+// when a == b, exactly kappa on coincident points).  The register forms evaluate a chunk in four rounds of four values per lane, which keeps
+// the fp64 kernels at 93 / 111 / 159 VGPRs (four, four and three waves per SIMD): with one wave per SIMD the load -> LDS -> barrier of every
+// chunk was exposed and the kernel ran 3.8 times slower.  Beyond d = 16 the coordinates go through LDS, 16 at a time.  D has col = i, so rows
+// of Yt are written in runs of 16 neighbouring elements; the second launch of a cut range adds diag_add Vt as the direct store does.
 //
 // stpy_pcg.  Ordinary preconditioned CG per column with M^-1 = I - G G^T (two NT products on the library's MFMA contraction per iteration).
 // One workgroup per column does that column's dot products (double accumulation, fixed order) and updates with scalars that never leave
 // the device; a frozen column is skipped by every kernel that writes X, R, P or its counter.
 #include "common.h"
-#include "pchol.hip"          // pc_phi / pc_fma: the one direct-difference evaluator
-
-#include <math.h>
+#include "kmv_pair.h"
 
 namespace stpy {
 
 namespace {
 
-constexpr int KM_THREADS = 256;
-constexpr int KM_TILE = 64;            // output points of a workgroup (16 per wave)
-constexpr int KM_JC = 64;              // contracted points per LDS chunk
 constexpr int KM_TC = 64;              // right-hand sides per pass (4 accumulator tuples)
-constexpr int KM_CS = KM_TC + 1;       // row stride of the Vt block in LDS
-constexpr int KM_FILL = 256;           // below this many output tiles the j range is cut ...
-constexpr int KM_SPLIT_TARGET = 512;   // ... into pieces, up to this many workgroups
-constexpr int KM_MAX_SPLIT = 64;
-constexpr int KM_SPLIT_MIN_J = 4 * KM_JC;          // a piece is at least this long
-
-// four kernel values at once, the kind decided once for the four: pc_phi of pchol.hip entry by entry (the same bits)
-template <typename T>
-__device__ __forceinline__ void km_phi4(int kind, const T* r2, T* out)
-{
-	switch (kind) {
-	case STPY_K_SE:
-#pragma unroll
-		for (int u = 0; u < 4; ++u) out[u] = pc_phi(STPY_K_SE, r2[u]);
-		break;
-	case STPY_K_MATERN12:
-#pragma unroll
-		for (int u = 0; u < 4; ++u) out[u] = pc_phi(STPY_K_MATERN12, r2[u]);
-		break;
-	case STPY_K_MATERN32:
-#pragma unroll
-		for (int u = 0; u < 4; ++u) out[u] = pc_phi(STPY_K_MATERN32, r2[u]);
-		break;
-	default:
-#pragma unroll
-		for (int u = 0; u < 4; ++u) out[u] = pc_phi(STPY_K_MATERN52, r2[u]);
-		break;
-	}
-}
 
 template <typename T>
 struct KmvArgs {
@@ -71,20 +29,20 @@ struct KmvArgs {
 
 // DC coordinates at a time; ONE: d <= DC, the a coordinates and the lengthscales are loaded once into registers
 template <typename T, int DC, bool ONE>
-__global__ __launch_bounds__(KM_THREADS, ONE ? 3 : 1)          // (second figure: waves per SIMD the register budget must allow)
+__global__ __launch_bounds__(KP_THREADS, ONE ? 3 : 1)          // (second figure: waves per SIMD the register budget must allow)
 void kmv_kernel(KmvArgs<T> g)
 {
 	typedef typename Mfma<T>::v4 v4;
-	__shared__ T sv[KM_JC][KM_CS];
-	__shared__ T sb[DC][KM_JC];
-	__shared__ T sa[ONE ? 1 : DC][KM_TILE];
+	__shared__ T sv[KP_JC][KM_TC + 1];
+	__shared__ T sb[DC][KP_JC];
+	__shared__ T sa[ONE ? 1 : DC][KP_TILE];
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
-	const int64_t i0 = (int64_t)blockIdx.x * KM_TILE;
+	const int64_t i0 = (int64_t)blockIdx.x * KP_TILE;
 	const int64_t i = i0 + 16 * w + li;
 	const int c0 = (int)blockIdx.z * KM_TC;
 	const int nb = min(4, (g.t - c0 + 15) >> 4);
-	const int64_t jb64 = (int64_t)blockIdx.y * g.jper;
-	const int jb = jb64 < g.q ? (int)jb64 : g.q, je = jb64 + g.jper < g.q ? (int)(jb64 + g.jper) : g.q;
+	int jb, je;
+	kp_range(g.jper, g.q, jb, je);
 	v4 acc[4];
 #pragma unroll
 	for (int b = 0; b < 4; ++b) acc[b] = v4{(T)0, (T)0, (T)0, (T)0};
@@ -98,7 +56,7 @@ void kmv_kernel(KmvArgs<T> g)
 			av[k] = (in && i < g.n) ? g.a[i * g.lda + c] : (T)0;
 		}
 	}
-	for (int64_t j0 = jb; j0 < je; j0 += KM_JC) {          // (64 bits: j0 + 64 may pass 2^31)
+	for (int64_t j0 = jb; j0 < je; j0 += KP_JC) {          // (64 bits: j0 + 64 may pass 2^31)
 		__syncthreads();                                              // (the previous chunk has been read)
 		for (int cc = w; cc < 16 * nb; cc += 4) {
 			const int c = c0 + cc;
@@ -106,7 +64,7 @@ void kmv_kernel(KmvArgs<T> g)
 			sv[lane][cc] = (c < g.t && j < je) ? g.Vt[(int64_t)c * g.ldv + j] : (T)0;
 		}
 		if (ONE) {
-			for (int e = tid; e < DC * KM_JC; e += KM_THREADS) {
+			for (int e = tid; e < DC * KP_JC; e += KP_THREADS) {
 				const int k = e >> 6, jj = e & 63;
 				const int64_t j = j0 + jj;
 				sb[k][jj] = (k < g.d && j < je) ? g.b[j * g.ldb + (g.cols ? g.cols[k] : k)] : (T)0;
@@ -142,7 +100,7 @@ void kmv_kernel(KmvArgs<T> g)
 			for (int s = 0; s < 16; ++s) r2[s] = (T)0;
 			for (int k0 = 0; k0 < g.d; k0 += DC) {
 				if (k0 > 0) __syncthreads();
-				for (int e = tid; e < DC * KM_JC; e += KM_THREADS) {
+				for (int e = tid; e < DC * KP_JC; e += KP_THREADS) {
 					const int k = e >> 6, jj = e & 63, kk = k0 + k;
 					const int64_t j = j0 + jj;
 					const int c = kk < g.d ? (g.cols ? g.cols[kk] : kk) : 0;
@@ -199,10 +157,10 @@ void kmv_kernel(KmvArgs<T> g)
 
 // Yt = the pieces added in piece order (+ diag_add Vt); with nsplit == 0 (q == 0) the zero fill
 template <typename T>
-__global__ __launch_bounds__(KM_THREADS)
+__global__ __launch_bounds__(KP_THREADS)
 void kmv_reduce_kernel(KmvArgs<T> g)
 {
-	const int64_t i = (int64_t)blockIdx.x * KM_THREADS + threadIdx.x;
+	const int64_t i = (int64_t)blockIdx.x * KP_THREADS + threadIdx.x;
 	if (i >= g.n) return;
 	for (int c = (int)blockIdx.y; c < g.t; c += (int)gridDim.y) {
 		T y = (T)0;
@@ -212,51 +170,35 @@ void kmv_reduce_kernel(KmvArgs<T> g)
 	}
 }
 
-// pieces of the j range for (n, q, t): 1 unless the output tiles leave most of the chip idle
-inline int kmv_nsplit(int64_t n, int64_t q, int64_t t)
-{
-	const int64_t tiles = ((n + KM_TILE - 1) / KM_TILE) * ((t + KM_TC - 1) / KM_TC);
-	if (tiles >= KM_FILL) return 1;
-	int64_t s = (KM_SPLIT_TARGET + tiles - 1) / tiles;
-	const int64_t by_q = (q + KM_SPLIT_MIN_J - 1) / KM_SPLIT_MIN_J;
-	if (s > by_q) s = by_q;
-	if (s > KM_MAX_SPLIT) s = KM_MAX_SPLIT;
-	return s < 1 ? 1 : (int)s;
-}
-
-// An upper bound of nsplit * t * n elements that does not decrease in n, q or t: the split happens below KM_FILL tiles only, where
-// nsplit <= KM_SPLIT_TARGET / tiles + 1 and n <= 64 tiles / passes, so nsplit n t <= (KM_SPLIT_TARGET + KM_FILL) 64 min(t, 64).
+// An upper bound of nsplit * t * n elements that does not decrease in n, q or t: the split happens below KP_FILL tiles only, where
+// nsplit <= KP_SPLIT_TARGET / tiles + 1 and n <= 64 tiles / passes, so nsplit n t <= (KP_SPLIT_TARGET + KP_FILL) 64 min(t, 64).
 inline int64_t kmv_workspace_bytes(int dtype, int64_t t)
 {
 	const int64_t esz = dtype == STPY_F32 ? 4 : 8;
 	const int64_t tc = t < 1 ? 1 : (t < KM_TC ? t : KM_TC);
-	return (int64_t)(KM_SPLIT_TARGET + KM_FILL) * KM_TILE * tc * esz;
+	return (int64_t)(KP_SPLIT_TARGET + KP_FILL) * KP_TILE * tc * esz;
 }
 
 template <typename T>
 int kmv(int kind, const T* a, int64_t n, int64_t lda, const T* b, int64_t q, int64_t ldb, int d, const int32_t* cols, const T* inv_ls,
         double kappa, double diag_add, const T* Vt, int64_t t, int64_t ldv, T* Yt, int64_t ldy, void* work, hipStream_t st)
 {
-	const int nsplit = q == 0 ? 0 : kmv_nsplit(n, q, t);
-	int64_t jper = q;
-	if (nsplit > 1) {
-		jper = (q + nsplit - 1) / nsplit;
-		jper = (jper + KM_JC - 1) / KM_JC * KM_JC;
-		if ((int64_t)nsplit * t * n * (int64_t)sizeof(T) > kmv_workspace_bytes(sizeof(T) == 4 ? STPY_F32 : STPY_F64, t)) {          // (cannot happen: see the bound)
-			set_error("stpy_kmv: internal: %d pieces of %lld x %lld exceed the workspace bound", nsplit, (long long)t, (long long)n);
-			return -21;
-		}
+	const int64_t passes = (t + KM_TC - 1) / KM_TC;
+	const int nsplit = q == 0 ? 0 : kp_split(kp_tiles(n) * passes, q, KP_MAX_SPLIT);
+	if (nsplit > 1 && (int64_t)nsplit * t * n * (int64_t)sizeof(T) > kmv_workspace_bytes(sizeof(T) == 4 ? STPY_F32 : STPY_F64, t)) {          // (cannot happen: see the bound)
+		set_error("stpy_kmv: internal: %d pieces of %lld x %lld exceed the workspace bound", nsplit, (long long)t, (long long)n);
+		return -21;
 	}
-	KmvArgs<T> g{a, lda, (int)n, b, ldb, (int)q, d, cols, inv_ls, (T)kappa, (T)diag_add, kind, Vt, ldv, (int)t, Yt, ldy, (T*)work, nsplit, (int)jper};
+	KmvArgs<T> g{a, lda, (int)n, b, ldb, (int)q, d, cols, inv_ls, (T)kappa, (T)diag_add, kind, Vt, ldv, (int)t, Yt, ldy, (T*)work, nsplit, (int)kp_piece_length(q, nsplit)};
 	if (nsplit >= 1) {
-		const dim3 grid((unsigned)((n + KM_TILE - 1) / KM_TILE), (unsigned)nsplit, (unsigned)((t + KM_TC - 1) / KM_TC));
-		if (d <= 4) hipLaunchKernelGGL((kmv_kernel<T, 4, true>), grid, dim3(KM_THREADS), 0, st, g);
-		else if (d <= 8) hipLaunchKernelGGL((kmv_kernel<T, 8, true>), grid, dim3(KM_THREADS), 0, st, g);
-		else if (d <= 16) hipLaunchKernelGGL((kmv_kernel<T, 16, true>), grid, dim3(KM_THREADS), 0, st, g);
-		else hipLaunchKernelGGL((kmv_kernel<T, 16, false>), grid, dim3(KM_THREADS), 0, st, g);
+		const dim3 grid((unsigned)kp_tiles(n), (unsigned)nsplit, (unsigned)passes);
+		if (d <= 4) hipLaunchKernelGGL((kmv_kernel<T, 4, true>), grid, dim3(KP_THREADS), 0, st, g);
+		else if (d <= 8) hipLaunchKernelGGL((kmv_kernel<T, 8, true>), grid, dim3(KP_THREADS), 0, st, g);
+		else if (d <= 16) hipLaunchKernelGGL((kmv_kernel<T, 16, true>), grid, dim3(KP_THREADS), 0, st, g);
+		else hipLaunchKernelGGL((kmv_kernel<T, 16, false>), grid, dim3(KP_THREADS), 0, st, g);
 	}
 	if (nsplit != 1)
-		hipLaunchKernelGGL(kmv_reduce_kernel<T>, dim3((unsigned)((n + KM_THREADS - 1) / KM_THREADS), (unsigned)(t < 64 ? t : 64)), dim3(KM_THREADS), 0, st, g);
+		hipLaunchKernelGGL(kmv_reduce_kernel<T>, dim3((unsigned)((n + KP_THREADS - 1) / KP_THREADS), (unsigned)(t < 64 ? t : 64)), dim3(KP_THREADS), 0, st, g);
 	return check_launch("stpy_kmv");
 }
 
@@ -301,20 +243,9 @@ inline PcgState<T> pcg_carve(void* work, int64_t n, int64_t t, int64_t r)
 	return s;
 }
 
-// sum over the workgroup in a fixed order, the same value in every thread; red: 4 words
-__device__ __forceinline__ double pcg_block_sum(double v, double* red)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	__syncthreads();                                                  // (red may still be read from the previous sum)
-	if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-	__syncthreads();
-	return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // X = 0, R = Z = B, the column norms; a zero column (or tol >= 1) starts frozen
 template <typename T>
-__global__ __launch_bounds__(KM_THREADS)
+__global__ __launch_bounds__(KP_THREADS)
 void pcg_init_kernel(PcgState<T> s, int n, const T* Bt, int64_t ldb, T* Xt, int64_t ldxt, double tol2)
 {
 	__shared__ double red[4];
@@ -325,12 +256,12 @@ void pcg_init_kernel(PcgState<T> s, int n, const T* Bt, int64_t ldb, T* Xt, int6
 	T* Z = s.Z + (int64_t)c * n;
 	T* P = s.P + (int64_t)c * n;
 	double bb = 0.0;
-	for (int i = threadIdx.x; i < n; i += KM_THREADS) {
+	for (int i = threadIdx.x; i < n; i += KP_THREADS) {
 		const T v = B[i];
 		X[i] = (T)0; R[i] = v; Z[i] = v; P[i] = (T)0;
 		bb += (double)v * (double)v;
 	}
-	bb = pcg_block_sum(bb, red);
+	bb = kp_block_sum(bb, red);
 	if (threadIdx.x == 0) {
 		s.col[c] = PcgCol{bb, bb, 0.0, 0.0};
 		s.its[c] = 0;
@@ -340,7 +271,7 @@ void pcg_init_kernel(PcgState<T> s, int n, const T* Bt, int64_t ldb, T* Xt, int6
 
 // pq = <P, Q>; X += alpha P, R -= alpha Q, Z = R, rr = <R, R>; the column freezes on convergence or on a curvature that is not positive and finite
 template <typename T>
-__global__ __launch_bounds__(KM_THREADS)
+__global__ __launch_bounds__(KP_THREADS)
 void pcg_step_kernel(PcgState<T> s, int n, T* Xt, int64_t ldxt, double tol2, PcgRec rec)
 {
 	__shared__ double red[4];
@@ -348,32 +279,32 @@ void pcg_step_kernel(PcgState<T> s, int n, T* Xt, int64_t ldxt, double tol2, Pcg
 	T* R = s.R + (int64_t)c * n;
 	T* Z = s.Z + (int64_t)c * n;
 	if (s.frozen[c]) {                                                // (workgroup-uniform) Z is the preconditioner's scratch: keep it finite
-		for (int i = threadIdx.x; i < n; i += KM_THREADS) Z[i] = R[i];
+		for (int i = threadIdx.x; i < n; i += KP_THREADS) Z[i] = R[i];
 		return;
 	}
 	const T* P = s.P + (int64_t)c * n;
 	const T* Q = s.Q + (int64_t)c * n;
 	T* X = Xt + (int64_t)c * ldxt;
 	double pq = 0.0;
-	for (int i = threadIdx.x; i < n; i += KM_THREADS) pq += (double)P[i] * (double)Q[i];
-	pq = pcg_block_sum(pq, red);
+	for (int i = threadIdx.x; i < n; i += KP_THREADS) pq += (double)P[i] * (double)Q[i];
+	pq = kp_block_sum(pq, red);
 	const PcgCol col = s.col[c];
 	const int it = s.its[c] + 1;
-	if (!(pq > 0.0) || !(pq <= 1.79769313486231570e308)) {
-		for (int i = threadIdx.x; i < n; i += KM_THREADS) Z[i] = R[i];
+	if (!(pq > 0.0) || !(pq <= F64_MAX)) {
+		for (int i = threadIdx.x; i < n; i += KP_THREADS) Z[i] = R[i];
 		if (threadIdx.x == 0) { s.its[c] = -it; s.frozen[c] = 1; }
 		return;
 	}
 	const T alpha = (T)(col.rz / pq);
 	if (rec.coef && threadIdx.x == 0 && it <= rec.cap) rec.coef[((int64_t)c * rec.cap + it - 1) * 2] = (double)alpha;
 	double rr = 0.0;
-	for (int i = threadIdx.x; i < n; i += KM_THREADS) {
+	for (int i = threadIdx.x; i < n; i += KP_THREADS) {
 		X[i] = pc_fma(alpha, P[i], X[i]);
 		const T rv = pc_fma(-alpha, Q[i], R[i]);
 		R[i] = rv; Z[i] = rv;
 		rr += (double)rv * (double)rv;
 	}
-	rr = pcg_block_sum(rr, red);
+	rr = kp_block_sum(rr, red);
 	if (threadIdx.x == 0) {
 		s.col[c].rr = rr;
 		s.its[c] = it;
@@ -383,7 +314,7 @@ void pcg_step_kernel(PcgState<T> s, int n, T* Xt, int64_t ldxt, double tol2, Pcg
 
 // rz' = <R, Z>; P = Z + (rz' / rz) P (first: P = Z).  A preconditioned residual product that is not positive and finite is flagged like a curvature.
 template <typename T>
-__global__ __launch_bounds__(KM_THREADS)
+__global__ __launch_bounds__(KP_THREADS)
 void pcg_dir_kernel(PcgState<T> s, int n, int first, PcgRec rec)
 {
 	__shared__ double red[4];
@@ -393,9 +324,9 @@ void pcg_dir_kernel(PcgState<T> s, int n, int first, PcgRec rec)
 	const T* Z = s.Z + (int64_t)c * n;
 	T* P = s.P + (int64_t)c * n;
 	double rz = 0.0;
-	for (int i = threadIdx.x; i < n; i += KM_THREADS) rz += (double)R[i] * (double)Z[i];
-	rz = pcg_block_sum(rz, red);
-	if (!(rz > 0.0) || !(rz <= 1.79769313486231570e308)) {
+	for (int i = threadIdx.x; i < n; i += KP_THREADS) rz += (double)R[i] * (double)Z[i];
+	rz = kp_block_sum(rz, red);
+	if (!(rz > 0.0) || !(rz <= F64_MAX)) {
 		if (threadIdx.x == 0) { s.its[c] = -(s.its[c] + 1); s.frozen[c] = 1; }
 		return;
 	}
@@ -405,13 +336,13 @@ void pcg_dir_kernel(PcgState<T> s, int n, int first, PcgRec rec)
 		if (first) rec.rz0[c] = rz;
 		else if (it <= rec.cap) rec.coef[((int64_t)c * rec.cap + it - 1) * 2 + 1] = (double)beta;
 	}
-	for (int i = threadIdx.x; i < n; i += KM_THREADS) P[i] = pc_fma(beta, P[i], Z[i]);
+	for (int i = threadIdx.x; i < n; i += KP_THREADS) P[i] = pc_fma(beta, P[i], Z[i]);
 	__syncthreads();                                                  // (every thread has read the old rz)
 	if (threadIdx.x == 0) s.col[c].rz = rz;
 }
 
 template <typename T>
-__global__ __launch_bounds__(KM_THREADS)
+__global__ __launch_bounds__(KP_THREADS)
 void pcg_finish_kernel(PcgState<T> s, int n, const T* Bt, int64_t ldb, const T* Xt, int64_t ldxt, T* relres, T* bx, int32_t* its)
 {
 	__shared__ double red[4];
@@ -419,8 +350,8 @@ void pcg_finish_kernel(PcgState<T> s, int n, const T* Bt, int64_t ldb, const T* 
 	const T* B = Bt + (int64_t)c * ldb;
 	const T* X = Xt + (int64_t)c * ldxt;
 	double v = 0.0;
-	for (int i = threadIdx.x; i < n; i += KM_THREADS) v += (double)B[i] * (double)X[i];
-	v = pcg_block_sum(v, red);
+	for (int i = threadIdx.x; i < n; i += KP_THREADS) v += (double)B[i] * (double)X[i];
+	v = kp_block_sum(v, red);
 	if (threadIdx.x == 0) {
 		const PcgCol col = s.col[c];
 		bx[c] = (T)v;
@@ -445,7 +376,7 @@ int pcg(int kind, const T* x, int64_t n, int64_t ldx, int d, const int32_t* cols
         double tol, int iters, int init, T* relres, T* bx, int32_t* its, void* work, hipStream_t st, PcgRec rec, const char* name)
 {
 	const PcgState<T> s = pcg_carve<T>(work, n, t, r);
-	const dim3 grid((unsigned)t), block(KM_THREADS);
+	const dim3 grid((unsigned)t), block(KP_THREADS);
 	const double tol2 = tol * tol;
 	int rc;
 	if (init) {
@@ -463,8 +394,6 @@ int pcg(int kind, const T* x, int64_t n, int64_t ldx, int d, const int32_t* cols
 	return check_launch(name);
 }
 
-inline bool km_finite(double v) { return v >= -1.79769313486231570e308 && v <= 1.79769313486231570e308; }
-
 }  // namespace
 
 }  // namespace stpy
@@ -480,7 +409,8 @@ static int pcg_checked(const char* name, int kind, int dtype, const void* x, int
                        void* relres, void* bx, int32_t* its,
                        void* work, int64_t work_bytes, void* stream, PcgRec rec)
 {
-	if (kind < STPY_K_SE || kind > STPY_K_MATERN52) { set_error("%s: kernel kind %d is not stationary (SE, MATERN12/32/52)", name, kind); return -1; }
+	int rc;
+	if ((rc = kp_check_stationary(name, kind)) != 0) return rc;
 	if (dtype != STPY_F64 && dtype != STPY_F32) { set_error("%s: unknown dtype %d (0 = float64, 1 = float32)", name, dtype); return -2; }
 	if (n < 0 || n >= ((int64_t)1 << 31)) { set_error("%s: n=%lld outside [0, 2^31)", name, (long long)n); return -4; }
 	if (n == 0) return 0;          // empty problem: nothing to write
@@ -488,19 +418,14 @@ static int pcg_checked(const char* name, int kind, int dtype, const void* x, int
 	if (t < 1 || t > 65535) { set_error("%s: t=%lld outside [1, 65535]", name, (long long)t); return -10; }
 	if (ldx < d) { set_error("%s: ldx=%lld below d=%d", name, (long long)ldx, d); return -5; }
 	if (ldb < n || ldxt < n) { set_error("%s: ldb=%lld or ldxt=%lld below n=%lld", name, (long long)ldb, (long long)ldxt, (long long)n); return -13; }
-	if (!km_finite(kappa) || !km_finite(diag_add)) { set_error("%s: kappa=%g and diag_add=%g must be finite", name, kappa, diag_add); return -11; }
-	if (!(tol >= 0.0) || !km_finite(tol)) { set_error("%s: tol=%g must be finite and not negative", name, tol); return -14; }
+	if (!is_finite(kappa) || !is_finite(diag_add)) { set_error("%s: kappa=%g and diag_add=%g must be finite", name, kappa, diag_add); return -11; }
+	if (!(tol >= 0.0) || !is_finite(tol)) { set_error("%s: tol=%g must be finite and not negative", name, tol); return -14; }
 	if (iters < 0) { set_error("%s: iters=%d", name, iters); return -15; }
 	if (r < 0 || r >= ((int64_t)1 << 31)) { set_error("%s: r=%lld outside [0, 2^31)", name, (long long)r); return -16; }
 	if (r > 0 && (!Gt || !Gn)) { set_error("%s: r=%lld with a null Gt or Gn", name, (long long)r); return -3; }
 	if (r > 0 && (ldgt < n || ldgn < r)) { set_error("%s: ldgt=%lld below n=%lld or ldgn=%lld below r=%lld", name, (long long)ldgt, (long long)n, (long long)ldgn, (long long)r); return -18; }
 	if (!x || !inv_ls || !Bt || !Xt || !relres || !bx || !its) { set_error("%s: null pointer", name); return -3; }
-	const int64_t need = pcg_workspace_bytes(dtype, n, t, r);
-	if (!work || work_bytes < need) {
-		set_error("%s: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", name, (long long)(work ? work_bytes : 0), (long long)need);
-		return -20;
-	}
-	if ((uintptr_t)work & 15) { set_error("%s: work must be 16-byte aligned", name); return -17; }
+	if ((rc = kp_check_work(name, work, work_bytes, pcg_workspace_bytes(dtype, n, t, r), 16)) != 0) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (dtype == STPY_F64)
 		return pcg<double>(kind, (const double*)x, n, ldx, d, cols, (const double*)inv_ls, kappa, diag_add, (const double*)Gt, ldgt, (const double*)Gn, ldgn, r,
@@ -521,23 +446,17 @@ int stpy_kmv(int kind, int dtype, const void* a, int64_t n, int64_t lda, const v
              int d, const int32_t* cols, const void* inv_ls, double kappa, double diag_add,
              const void* Vt, int64_t t, int64_t ldv, void* Yt, int64_t ldy, void* work, int64_t work_bytes, void* stream)
 {
-	if (kind < STPY_K_SE || kind > STPY_K_MATERN52) { set_error("stpy_kmv: kernel kind %d is not stationary (SE, MATERN12/32/52)", kind); return -1; }
-	if (dtype != STPY_F64 && dtype != STPY_F32) { set_error("stpy_kmv: unknown dtype %d (0 = float64, 1 = float32)", dtype); return -2; }
-	if (n < 0 || n >= ((int64_t)1 << 31) || q < 0 || q >= ((int64_t)1 << 31)) { set_error("stpy_kmv: n=%lld or q=%lld outside [0, 2^31)", (long long)n, (long long)q); return -4; }
+	const char* name = "stpy_kmv";
+	int rc;
+	if ((rc = kp_check_stationary(name, kind)) != 0 || (rc = kp_check_sizes(name, dtype, n, q)) != 0) return rc;
 	if (n == 0) return 0;          // empty output: nothing to write
 	if (d < 1) { set_error("stpy_kmv: d=%d", d); return -6; }
 	if (t < 1 || t > (int64_t)65535 * KM_TC) { set_error("stpy_kmv: t=%lld outside [1, %lld]", (long long)t, (long long)65535 * KM_TC); return -10; }
-	if (lda < d || ldb < d) { set_error("stpy_kmv: lda=%lld or ldb=%lld below d=%d", (long long)lda, (long long)ldb, d); return -5; }
+	if ((rc = kp_check_ld_points(name, lda, ldb, d)) != 0) return rc;
 	if (ldv < q || ldy < n) { set_error("stpy_kmv: ldv=%lld below q=%lld or ldy=%lld below n=%lld", (long long)ldv, (long long)q, (long long)ldy, (long long)n); return -13; }
-	if (!km_finite(kappa) || !km_finite(diag_add)) { set_error("stpy_kmv: kappa=%g and diag_add=%g must be finite", kappa, diag_add); return -11; }
+	if (!is_finite(kappa) || !is_finite(diag_add)) { set_error("stpy_kmv: kappa=%g and diag_add=%g must be finite", kappa, diag_add); return -11; }
 	if (diag_add != 0.0 && q != n) { set_error("stpy_kmv: diag_add=%g needs the same points on both sides, q=%lld != n=%lld", diag_add, (long long)q, (long long)n); return -12; }
-	if (!a || !inv_ls || !Yt || (q > 0 && (!b || !Vt))) { set_error("stpy_kmv: null pointer"); return -3; }          // (q == 0 reads neither b nor Vt)
-	const int64_t need = kmv_workspace_bytes(dtype, t);
-	if (!work || work_bytes < need) {
-		set_error("stpy_kmv: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", (long long)(work ? work_bytes : 0), (long long)need);
-		return -20;
-	}
-	if ((uintptr_t)work & 7) { set_error("stpy_kmv: work must be 8-byte aligned"); return -17; }
+	if ((rc = kp_check_pointers(name, a, b, q, inv_ls, Vt, Yt)) != 0 || (rc = kp_check_work(name, work, work_bytes, kmv_workspace_bytes(dtype, t), 8)) != 0) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (dtype == STPY_F64)
 		return kmv<double>(kind, (const double*)a, n, lda, (const double*)b, q, ldb, d, cols, (const double*)inv_ls, kappa, diag_add,

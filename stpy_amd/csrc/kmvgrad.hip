@@ -2,72 +2,21 @@
 //   out[c, k] = sum_ij u_ci v_cj kappa chi(rho_ij) e_ijk^2 (k < d),   out[c, d] = u_c^T K v_c,   out[c, d + 1] = <u_c, v_c>,
 // with e_ijk = (x_i - x_j)[cols[k]] * inv_ls[k], rho = sum_k e_k^2 and chi = 2 dphi/drho: d(u^T K v)/d inv_ls[k] = out[c, k] / inv_ls[k].  K is never formed.
 //
-// The launch shape is that of stpy_kmv (kmv.hip): a workgroup of four waves owns 64 points i, 16 per wave, and walks j in chunks of 64 through
-// LDS.  The 16x16x4 MFMA runs with A = a fragment of Vt (row = pair c, k = j) and B = a 4 x 16 fragment that each lane evaluates itself for
-// the ONE pair (i, j) its operand slot wants: the lane forms the d scaled differences once, from them rho, phi and chi (the evaluator of
-// pchol.hip: the same bits as stpy_kmv for the value column), and issues d + 1 MFMAs against the same A fragment with B = kappa chi e_k^2 and
-// B = kappa phi.  The per-pair cost is d + 1 matrix instructions for 16 pairs of rows, not 16 (d + 1) fused multiply-adds.
-// d + 1 accumulator tuples serve ONE block of 16 pairs (68 fp64 values per lane at d = 16), so further blocks of 16 pairs go over blockIdx.z.
-// Every accumulator is a C = D chain on its own, fully live tuple (the fp64 rule of potrf.hip).  Coordinates stay in registers up to d = 16
-// (instantiations for 4, 8 and 16); beyond, rho is gathered through LDS 8 coordinates at a time and a workgroup owns the outputs of ONE
-// group of 8 coordinates (blockIdx.z walks groups as well), so that the register budget does not depend on d.
+// The pair walker of kmv_pair.h (the design, the cut, the fp64 rule and the rho == 0 guard are stated there), square (x against x).  What this
+// file adds: the lane forms the d scaled differences of its pair once and issues d + 1 MFMAs against the same A fragment with B = kappa chi e_k^2
+// and B = kappa phi (the bits of stpy_kmv for the value column), so the per-pair cost is d + 1 matrix instructions for 16 pairs of rows, not
+// 16 (d + 1) fused multiply-adds.  d + 1 accumulator tuples serve ONE block of 16 pairs (68 fp64 values per lane at d = 16), so further blocks of
+// 16 pairs go over blockIdx.z.  Beyond d = 16, rho is gathered 8 coordinates at a time and a workgroup owns the outputs of ONE group of 8
+// coordinates (blockIdx.z walks groups as well), so that the register budget does not depend on d.
 // Epilogue: the D tile is multiplied by Ut[c, i], summed over the 16 lanes of a row by a butterfly and over the four waves in wave order, and
 // ONE partial row per workgroup and pair goes to `work`.  A second launch adds the partial rows in a fixed order (double accumulation) and
-// computes <u_c, v_c>.  No atomics, no spin-waits, no cooperative grid, no scratch; the same bits on every call and for every ldu / ldv.
-// When the output tiles are too few to fill the chip the j range is cut into blockIdx.y pieces, as in stpy_kmv.
-// A pair with rho == 0 contributes exactly 0 to the first d outputs (its e_k are 0; the guard keeps Matern 1/2, whose chi is -exp(-r) / r, from 0 / 0).
-#ifndef STPY_KMVGRAD_HIP
-#define STPY_KMVGRAD_HIP
+// computes <u_c, v_c>.
 #include "common.h"
-#include "pchol.hip"          // pc_phi / pc_fma: the one direct-difference evaluator
-
-#include <math.h>
+#include "kmv_pair.h"
 
 namespace stpy {
 
 namespace {
-
-constexpr int KD_THREADS = 256;
-constexpr int KD_TILE = 64;            // points i of a workgroup (16 per wave)
-constexpr int KD_JC = 64;              // contracted points per LDS chunk
-constexpr int KD_PB = 16;              // pairs (u_c, v_c) of a workgroup: one MFMA row block
-constexpr int KD_VS = KD_PB + 1;       // row stride of the Vt block in LDS
-constexpr int KD_FILL = 256;           // below this many workgroups the j range is cut ...
-constexpr int KD_SPLIT_TARGET = 512;   // ... into pieces, up to this many workgroups
-constexpr int KD_MAX_SPLIT = 64;
-constexpr int KD_SPLIT_MIN_J = 4 * KD_JC;
-constexpr int KD_GC = 8;               // coordinates of an output group beyond d = 16 (the general form)
-
-__device__ __forceinline__ double kd_exp(double a) { return exp(a); }
-__device__ __forceinline__ float kd_exp(float a) { return expf(a); }
-
-// phi (pc_phi: the bits of stpy_kmv) and chi = 2 dphi/drho of a scaled squared distance
-template <typename T>
-__device__ __forceinline__ void kd_phi_chi(int kind, T rho, T& phi, T& chi)
-{
-	switch (kind) {
-	case STPY_K_SE:
-		phi = pc_phi(STPY_K_SE, rho);
-		chi = -phi;
-		break;
-	case STPY_K_MATERN12:
-		phi = pc_phi(STPY_K_MATERN12, rho);
-		chi = -phi / pc_sqrt(rho);                                     // (rho == 0: masked by the caller)
-		break;
-	case STPY_K_MATERN32: {
-		const T r = pc_sqrt(rho) * (T)1.7320508075688772935;
-		phi = pc_phi(STPY_K_MATERN32, rho);
-		chi = (T)-3 * kd_exp(-r);
-		break;
-	}
-	default: {
-		const T r = pc_sqrt(rho) * (T)2.2360679774997896964;
-		phi = pc_phi(STPY_K_MATERN52, rho);
-		chi = (T)(-5.0 / 3.0) * ((T)1 + r) * kd_exp(-r);
-		break;
-	}
-	}
-}
 
 template <typename T>
 struct KdArgs {
@@ -75,36 +24,25 @@ struct KdArgs {
 	const T* Ut; int64_t ldu; const T* Vt; int64_t ldv; int t; T* out; int64_t ldo; T* part; int nsplit, jper, ntiles, nkc;
 };
 
-// sum over the workgroup in a fixed order, the same value in every thread; red: 4 words
-__device__ __forceinline__ double kd_block_sum(double v, double* red)
-{
-#pragma unroll
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	__syncthreads();                                                  // (red may still be read from the previous sum)
-	if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-	__syncthreads();
-	return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // DC coordinates at a time; ONE: d <= DC, the coordinates of i and the lengthscales are loaded once into registers and the workgroup owns
 // every output column; otherwise rho is gathered through LDS and the workgroup owns the columns of coordinate group blockIdx.z % nkc
 template <typename T, int DC, bool ONE>
-__global__ __launch_bounds__(KD_THREADS)
+__global__ __launch_bounds__(KP_THREADS)
 void kmvd_kernel(KdArgs<T> g)
 {
 	typedef typename Mfma<T>::v4 v4;
-	__shared__ T sv[KD_JC][KD_VS];
-	__shared__ T sb[DC][KD_JC];
-	__shared__ T sa[ONE ? 1 : DC][KD_TILE];
-	__shared__ T red[4][DC + 1][KD_PB];
+	__shared__ T sv[KP_JC][KP_PB + 1];
+	__shared__ T sb[DC][KP_JC];
+	__shared__ T sa[ONE ? 1 : DC][KP_TILE];
+	__shared__ T red[4][DC + 1][KP_PB];
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lk = lane >> 4;
-	const int64_t i0 = (int64_t)blockIdx.x * KD_TILE;
+	const int64_t i0 = (int64_t)blockIdx.x * KP_TILE;
 	const int64_t i = i0 + 16 * w + li;
 	const int kc = ONE ? 0 : (int)blockIdx.z % g.nkc;                  // coordinate group of the outputs
-	const int c0 = (ONE ? (int)blockIdx.z : (int)blockIdx.z / g.nkc) * KD_PB;
+	const int c0 = (ONE ? (int)blockIdx.z : (int)blockIdx.z / g.nkc) * KP_PB;
 	const int kb = kc * DC;
-	const int64_t jb64 = (int64_t)blockIdx.y * g.jper;
-	const int jb = jb64 < g.n ? (int)jb64 : g.n, je = jb64 + g.jper < g.n ? (int)(jb64 + g.jper) : g.n;
+	int jb, je;
+	kp_range(g.jper, g.n, jb, je);
 	v4 acc[DC + 1];
 #pragma unroll
 	for (int k = 0; k <= DC; ++k) acc[k] = v4{(T)0, (T)0, (T)0, (T)0};
@@ -117,15 +55,15 @@ void kmvd_kernel(KdArgs<T> g)
 		av[k] = (in && i < g.n) ? g.x[i * g.ldx + c] : (T)0;
 	}
 	constexpr int KD_UNROLL = DC <= 8 ? 2 : 1;
-	for (int64_t j0 = jb; j0 < je; j0 += KD_JC) {                         // (64 bits: j0 + 64 may pass 2^31)
+	for (int64_t j0 = jb; j0 < je; j0 += KP_JC) {                         // (64 bits: j0 + 64 may pass 2^31)
 		__syncthreads();                                              // (the previous chunk has been read)
-		for (int cc = w; cc < KD_PB; cc += 4) {
+		for (int cc = w; cc < KP_PB; cc += 4) {
 			const int c = c0 + cc;
 			const int64_t j = j0 + lane;
 			sv[lane][cc] = (c < g.t && j < je) ? g.Vt[(int64_t)c * g.ldv + j] : (T)0;
 		}
 		if (ONE) {
-			for (int e = tid; e < DC * KD_JC; e += KD_THREADS) {
+			for (int e = tid; e < DC * KP_JC; e += KP_THREADS) {
 				const int k = e >> 6, jj = e & 63;
 				const int64_t j = j0 + jj;
 				sb[k][jj] = (k < g.d && j < je) ? g.x[j * g.ldx + (g.cols ? g.cols[k] : k)] : (T)0;
@@ -144,7 +82,7 @@ void kmvd_kernel(KdArgs<T> g)
 				T phi, chi;
 				kd_phi_chi(g.kind, rho, phi, chi);
 				const bool in = j0 + jj < je;
-				const T wchi = (in && rho != (T)0) ? g.kappa * chi : (T)0;
+				const T wchi = (in && rho != (T)0) ? g.kappa * chi : (T)0;          // (the rho == 0 guard of kmv_pair.h)
 				const T wphi = in ? g.kappa * phi : (T)0;
 				const T a = sv[jj][li];
 #pragma unroll
@@ -157,7 +95,7 @@ void kmvd_kernel(KdArgs<T> g)
 			for (int s = 0; s < 16; ++s) rho[s] = (T)0;
 			for (int k0 = 0; k0 < g.d; k0 += DC) {
 				if (k0 > 0) __syncthreads();
-				for (int e = tid; e < DC * KD_JC; e += KD_THREADS) {
+				for (int e = tid; e < DC * KP_JC; e += KP_THREADS) {
 					const int k = e >> 6, jj = e & 63, kk = k0 + k;
 					const int64_t j = j0 + jj;
 					const int c = kk < g.d ? (g.cols ? g.cols[kk] : kk) : 0;
@@ -177,7 +115,7 @@ void kmvd_kernel(KdArgs<T> g)
 				}
 			}
 			__syncthreads();                                          // (the last round of rho has been read) the group's own coordinates of j
-			for (int e = tid; e < DC * KD_JC; e += KD_THREADS) {
+			for (int e = tid; e < DC * KP_JC; e += KP_THREADS) {
 				const int k = e >> 6, jj = e & 63, kk = kb + k;
 				const int64_t j = j0 + jj;
 				sb[k][jj] = (kk < g.d && j < je) ? g.x[j * g.ldx + (g.cols ? g.cols[kk] : kk)] : (T)0;
@@ -186,11 +124,8 @@ void kmvd_kernel(KdArgs<T> g)
 #pragma unroll
 			for (int s = 0; s < 16; ++s) {
 				const int jj = 4 * s + lk;
-				T phi, chi;
-				kd_phi_chi(g.kind, rho[s], phi, chi);
-				const bool in = j0 + jj < je;
-				const T wchi = (in && rho[s] != (T)0) ? g.kappa * chi : (T)0;
-				const T wphi = in ? g.kappa * phi : (T)0;
+				T wphi, wchi;
+				kp_weights(g.kind, g.kappa, rho[s], j0 + jj < je, wphi, wchi);
 				const T a = sv[jj][li];
 #pragma unroll
 				for (int k = 0; k < DC; ++k) {
@@ -220,7 +155,7 @@ void kmvd_kernel(KdArgs<T> g)
 	}
 	__syncthreads();
 	const int64_t p = (int64_t)blockIdx.y * g.ntiles + blockIdx.x;
-	for (int e = tid; e < (DC + 1) * KD_PB; e += KD_THREADS) {
+	for (int e = tid; e < (DC + 1) * KP_PB; e += KP_THREADS) {
 		const int k = e >> 4, row = e & 15, c = c0 + row;
 		const int kk = k == DC ? g.d : kb + k;                         // output column: a coordinate of this group, or the value (group 0 writes it)
 		if (c >= g.t || (k == DC ? kc != 0 : kk >= g.d)) continue;
@@ -230,7 +165,7 @@ void kmvd_kernel(KdArgs<T> g)
 
 // out[c, 0 .. d] = the partial rows added in a fixed order, out[c, d + 1] = <u_c, v_c>; one workgroup per pair.  No partial rows (n == 0): zeros.
 template <typename T>
-__global__ __launch_bounds__(KD_THREADS)
+__global__ __launch_bounds__(KP_THREADS)
 void kmvd_reduce_kernel(KdArgs<T> g)
 {
 	__shared__ double red[4];
@@ -238,28 +173,20 @@ void kmvd_reduce_kernel(KdArgs<T> g)
 	const int64_t np = (int64_t)g.nsplit * g.ntiles;
 	for (int kk = 0; kk <= g.d; ++kk) {
 		double v = 0.0;
-		for (int64_t p = threadIdx.x; p < np; p += KD_THREADS) v += (double)g.part[(p * g.t + c) * (g.d + 1) + kk];
-		v = kd_block_sum(v, red);
+		for (int64_t p = threadIdx.x; p < np; p += KP_THREADS) v += (double)g.part[(p * g.t + c) * (g.d + 1) + kk];
+		v = kp_block_sum(v, red);
 		if (threadIdx.x == 0) g.out[(int64_t)c * g.ldo + kk] = (T)v;
 	}
 	double v = 0.0;
-	for (int i = threadIdx.x; i < g.n; i += KD_THREADS) v += (double)g.Ut[(int64_t)c * g.ldu + i] * (double)g.Vt[(int64_t)c * g.ldv + i];
-	v = kd_block_sum(v, red);
+	for (int i = threadIdx.x; i < g.n; i += KP_THREADS) v += (double)g.Ut[(int64_t)c * g.ldu + i] * (double)g.Vt[(int64_t)c * g.ldv + i];
+	v = kp_block_sum(v, red);
 	if (threadIdx.x == 0) g.out[(int64_t)c * g.ldo + g.d + 1] = (T)v;
 }
 
-// pieces of the j range for (n, d, t): 1 unless the workgroups leave most of the chip idle
+// pieces of the j range for (n, d, t); 0 for n == 0
 inline int kd_nsplit(int64_t n, int d, int64_t t)
 {
-	if (n < 1) return 0;
-	const int64_t groups = d <= 16 ? 1 : ((int64_t)d + KD_GC - 1) / KD_GC;
-	const int64_t tiles = ((n + KD_TILE - 1) / KD_TILE) * ((t + KD_PB - 1) / KD_PB) * groups;
-	if (tiles >= KD_FILL) return 1;
-	int64_t s = (KD_SPLIT_TARGET + tiles - 1) / tiles;
-	const int64_t by_n = (n + KD_SPLIT_MIN_J - 1) / KD_SPLIT_MIN_J;
-	if (s > by_n) s = by_n;
-	if (s > KD_MAX_SPLIT) s = KD_MAX_SPLIT;
-	return s < 1 ? 1 : (int)s;
+	return n < 1 ? 0 : kp_split(kp_tiles(n) * kp_row_blocks(t) * kp_coord_groups(d), n, KP_MAX_SPLIT);
 }
 
 // one partial row of d + 1 sums per workgroup (tile of i, piece of j) and pair
@@ -269,7 +196,7 @@ inline int64_t kd_workspace_bytes(int dtype, int64_t n, int d, int64_t t)
 	if (n < 1) n = 1;
 	if (t < 1) t = 1;
 	if (d < 1) d = 1;
-	const int64_t rows = ((n + KD_TILE - 1) / KD_TILE) * kd_nsplit(n, d, t);
+	const int64_t rows = kp_tiles(n) * kd_nsplit(n, d, t);
 	return (rows * t * ((int64_t)d + 1) * esz + 255) / 256 * 256;
 }
 
@@ -278,26 +205,19 @@ int kmv_dtheta(int kind, const T* x, int64_t n, int64_t ldx, int d, const int32_
                const T* Ut, int64_t ldu, const T* Vt, int64_t ldv, int64_t t, T* out, int64_t ldo, void* work, hipStream_t st)
 {
 	const int nsplit = kd_nsplit(n, d, t);
-	const int ntiles = (int)((n + KD_TILE - 1) / KD_TILE);
-	const int nkc = d <= 16 ? 1 : (d + KD_GC - 1) / KD_GC;
-	int64_t jper = n;
-	if (nsplit > 1) {
-		jper = (n + nsplit - 1) / nsplit;
-		jper = (jper + KD_JC - 1) / KD_JC * KD_JC;
-	}
-	KdArgs<T> g{x, ldx, (int)n, d, cols, inv_ls, (T)kappa, kind, Ut, ldu, Vt, ldv, (int)t, out, ldo, (T*)work, nsplit, (int)jper, ntiles, nkc};
+	const int ntiles = (int)kp_tiles(n);
+	const int nkc = (int)kp_coord_groups(d);
+	KdArgs<T> g{x, ldx, (int)n, d, cols, inv_ls, (T)kappa, kind, Ut, ldu, Vt, ldv, (int)t, out, ldo, (T*)work, nsplit, (int)kp_piece_length(n, nsplit), ntiles, nkc};
 	if (nsplit >= 1) {
-		const dim3 grid((unsigned)ntiles, (unsigned)nsplit, (unsigned)(((t + KD_PB - 1) / KD_PB) * nkc));
-		if (d <= 4) hipLaunchKernelGGL((kmvd_kernel<T, 4, true>), grid, dim3(KD_THREADS), 0, st, g);
-		else if (d <= 8) hipLaunchKernelGGL((kmvd_kernel<T, 8, true>), grid, dim3(KD_THREADS), 0, st, g);
-		else if (d <= 16) hipLaunchKernelGGL((kmvd_kernel<T, 16, true>), grid, dim3(KD_THREADS), 0, st, g);
-		else hipLaunchKernelGGL((kmvd_kernel<T, KD_GC, false>), grid, dim3(KD_THREADS), 0, st, g);
+		const dim3 grid((unsigned)ntiles, (unsigned)nsplit, (unsigned)(kp_row_blocks(t) * nkc));
+		if (d <= 4) hipLaunchKernelGGL((kmvd_kernel<T, 4, true>), grid, dim3(KP_THREADS), 0, st, g);
+		else if (d <= 8) hipLaunchKernelGGL((kmvd_kernel<T, 8, true>), grid, dim3(KP_THREADS), 0, st, g);
+		else if (d <= 16) hipLaunchKernelGGL((kmvd_kernel<T, 16, true>), grid, dim3(KP_THREADS), 0, st, g);
+		else hipLaunchKernelGGL((kmvd_kernel<T, KP_GC, false>), grid, dim3(KP_THREADS), 0, st, g);
 	}
-	hipLaunchKernelGGL(kmvd_reduce_kernel<T>, dim3((unsigned)t), dim3(KD_THREADS), 0, st, g);
+	hipLaunchKernelGGL(kmvd_reduce_kernel<T>, dim3((unsigned)t), dim3(KP_THREADS), 0, st, g);
 	return check_launch("stpy_kmv_dtheta");
 }
-
-inline bool kd_finite(double v) { return v >= -1.79769313486231570e308 && v <= 1.79769313486231570e308; }
 
 }  // namespace
 
@@ -317,27 +237,21 @@ int stpy_kmv_dtheta(int kind, int dtype, const void* x, int64_t n, int64_t ldx, 
                     const void* Ut, int64_t ldu, const void* Vt, int64_t ldv, int64_t t,
                     void* out, int64_t ldo, void* work, int64_t work_bytes, void* stream)
 {
-	if (kind < STPY_K_SE || kind > STPY_K_MATERN52) { set_error("stpy_kmv_dtheta: kernel kind %d is not stationary (SE, MATERN12/32/52)", kind); return -1; }
+	int rc;
+	if ((rc = kp_check_stationary("stpy_kmv_dtheta", kind)) != 0) return rc;
 	if (dtype != STPY_F64 && dtype != STPY_F32) { set_error("stpy_kmv_dtheta: unknown dtype %d (0 = float64, 1 = float32)", dtype); return -2; }
 	if (n < 0 || n >= ((int64_t)1 << 31)) { set_error("stpy_kmv_dtheta: n=%lld outside [0, 2^31)", (long long)n); return -4; }
 	if (d < 1) { set_error("stpy_kmv_dtheta: d=%d", d); return -6; }
-	const int64_t zblocks = (t < 1 ? 0 : (t + KD_PB - 1) / KD_PB) * (d <= 16 ? 1 : ((int64_t)d + KD_GC - 1) / KD_GC);
+	const int64_t zblocks = (t < 1 ? 0 : kp_row_blocks(t)) * kp_coord_groups(d);
 	if (t < 1 || zblocks > 65535) { set_error("stpy_kmv_dtheta: t=%lld outside [1, 65535 * 16 / groups] (groups = 1 up to d = 16, ceil(d / 8) beyond)", (long long)t); return -10; }
 	if (ldx < d) { set_error("stpy_kmv_dtheta: ldx=%lld below d=%d", (long long)ldx, d); return -5; }
 	if (ldu < n || ldv < n || ldo < (int64_t)d + 2) {
 		set_error("stpy_kmv_dtheta: ldu=%lld or ldv=%lld below n=%lld, or ldo=%lld below d + 2 = %lld", (long long)ldu, (long long)ldv, (long long)n, (long long)ldo, (long long)d + 2);
 		return -13;
 	}
-	if (!kd_finite(kappa)) { set_error("stpy_kmv_dtheta: kappa=%g must be finite", kappa); return -11; }
+	if (!is_finite(kappa)) { set_error("stpy_kmv_dtheta: kappa=%g must be finite", kappa); return -11; }
 	if (!out || (n > 0 && (!x || !inv_ls || !Ut || !Vt))) { set_error("stpy_kmv_dtheta: null pointer"); return -3; }          // (n == 0 reads nothing)
-	if (n > 0) {
-		const int64_t need = kd_workspace_bytes(dtype, n, d, t);
-		if (!work || work_bytes < need) {
-			set_error("stpy_kmv_dtheta: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", (long long)(work ? work_bytes : 0), (long long)need);
-			return -20;
-		}
-		if ((uintptr_t)work & 7) { set_error("stpy_kmv_dtheta: work must be 8-byte aligned"); return -17; }
-	}
+	if (n > 0 && (rc = kp_check_work("stpy_kmv_dtheta", work, work_bytes, kd_workspace_bytes(dtype, n, d, t), 8)) != 0) return rc;
 	hipStream_t st = (hipStream_t)stream;
 	if (dtype == STPY_F64)
 		return kmv_dtheta<double>(kind, (const double*)x, n, ldx, d, cols, (const double*)inv_ls, kappa, (const double*)Ut, ldu, (const double*)Vt, ldv, t,
@@ -347,5 +261,3 @@ int stpy_kmv_dtheta(int kind, int dtype, const void* x, int64_t n, int64_t ldx, 
 }
 
 }  // extern "C"
-
-#endif

@@ -17,9 +17,8 @@
 // Traffic: step j reads j * n elements, a run of rank r reads esz * n * r (r - 1) / 2 bytes; the kernel is a streaming read, bounded by
 // HBM once Ft outgrows the Infinity Cache.  The redundant part -- every workgroup gathers Ft[0:j, p] (j scattered lines) and reads all
 // the partials -- is j / (64 V) of that.
-#ifndef STPY_PCHOL_HIP          // (kmv.hip includes this file for the kernel evaluator; api.hip includes both)
-#define STPY_PCHOL_HIP
 #include "common.h"
+#include "kmv_pair.h"          // pc_phi / pc_fma / pc_sqrt: the one direct-difference evaluator, shared with the matrix-free products
 
 #include <limits.h>
 #include <math.h>
@@ -43,32 +42,6 @@ struct PcholArgs {
 	const T* x; int64_t ldx; int n, d; const int32_t* cols; const T* inv_ls; T kappa; double thr; int kind;
 	T* Ft; int64_t ldf; T* dres; int32_t* piv; int32_t* rank; PcholPart* part; int nblk, m, vec_ok;
 };
-
-// kappa-free kernel value from the scaled squared distance
-__device__ __forceinline__ double pc_phi(int kind, double r2)
-{
-	switch (kind) {
-	case STPY_K_SE: return exp(-0.5 * r2);
-	case STPY_K_MATERN12: return exp(-sqrt(r2));
-	case STPY_K_MATERN32: { const double r = sqrt(r2) * 1.7320508075688772935; return (1.0 + r) * exp(-r); }
-	default: { const double r = sqrt(r2) * 2.2360679774997896964; return (1.0 + r + r * r / 3.0) * exp(-r); }
-	}
-}
-
-__device__ __forceinline__ float pc_phi(int kind, float r2)
-{
-	switch (kind) {
-	case STPY_K_SE: return expf(-0.5f * r2);
-	case STPY_K_MATERN12: return expf(-sqrtf(r2));
-	case STPY_K_MATERN32: { const float r = sqrtf(r2) * 1.7320508075688772935f; return (1.0f + r) * expf(-r); }
-	default: { const float r = sqrtf(r2) * 2.2360679774997896964f; return (1.0f + r + r * r / 3.0f) * expf(-r); }
-	}
-}
-
-__device__ __forceinline__ double pc_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ __forceinline__ float pc_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double pc_sqrt(double a) { return sqrt(a); }
-__device__ __forceinline__ float pc_sqrt(float a) { return sqrtf(a); }
 
 // the argmax order: larger value first, then the lower index.  A NaN is never better than anything.
 __device__ __forceinline__ bool pc_better(double v, int i, double bv, int bi) { return v > bv || (v == bv && i < bi); }
@@ -256,7 +229,7 @@ int stpy_pchol(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d
 	if (d < 1) { set_error("stpy_pchol: d=%d", d); return -6; }
 	if (ldx < d) { set_error("stpy_pchol: ldx=%lld below d=%d", (long long)ldx, d); return -5; }
 	if (m < 1 || m > n || m > PC_MAX_M) { set_error("stpy_pchol: m=%lld outside [1, min(n=%lld, %d)]", (long long)m, (long long)n, PC_MAX_M); return -10; }
-	if (!(tol >= 0.0) || !(tol <= 1.79769313486231570e308)) { set_error("stpy_pchol: tol=%g must be finite and not negative", tol); return -11; }
+	if (!(tol >= 0.0) || !is_finite(tol)) { set_error("stpy_pchol: tol=%g must be finite and not negative", tol); return -11; }
 	if (ldf < n) { set_error("stpy_pchol: ldf=%lld below n=%lld", (long long)ldf, (long long)n); return -13; }
 	if (!x || !inv_ls || !Ft || !dres || !piv || !rank_dev || !work) { set_error("stpy_pchol: null pointer"); return -3; }
 	const int64_t need = pchol_workspace_bytes(dtype, n);
@@ -273,4 +246,3 @@ int stpy_pchol(int kind, int dtype, const void* x, int64_t n, int64_t ldx, int d
 
 }  // extern "C"
 
-#endif  // STPY_PCHOL_HIP

@@ -159,7 +159,7 @@ def test_kappa_is_a_pure_scale(L, dt):
 @pytest.mark.parametrize("d", (3, 20))
 def test_kmv_products_on_ard_and_off_centre_points(L, d, t, dt):
 	"""A real V: per entry 2 eps (q + d + 8) (|K| |V|), the bound of tests/test_gpu_kmv.py, with K the longdouble truth.  n = 5 against q = 1300
-	has its j range cut into 6 pieces (kmv_nsplit), n = q = 129 (a is b, diag_add = 0.1) runs uncut.  Each twin gives the same bits."""
+	has its j range cut into 6 pieces (kp_split), n = q = 129 (a is b, diag_add = 0.1) runs uncut.  Each twin gives the same bits."""
 	T = E.DTYPES[dt]
 	worst = 0.0
 	for (n, q, same) in ((5, 1300, False), (129, 129, True)):

@@ -220,3 +220,27 @@ def test_kmv_dxx_empty_problems(dtype_name):
 		_lib.kmv_dxx(3, torch.zeros((n, 4), dtype=dt, device=dev), torch.empty((0, 4), dtype=dt, device=dev), torch.empty((3, 0), dtype=dt, device=dev), out, il)
 		full = store.cpu().numpy()
 		assert np.all(full[:, :n, :nc] == 0) and np.all(np.isnan(full[:, n:, :])) and np.all(np.isnan(full[:, :, nc:]))
+
+
+@pytest.mark.parametrize("dtype_name", DTYPES)
+@pytest.mark.parametrize("with_cols", [False, True], ids=["plain", "cols"])
+@pytest.mark.parametrize("kind", XO.HESSIAN_KINDS)
+@pytest.mark.parametrize("d", [3, 8, 16])
+@pytest.mark.parametrize("t", [3, 17])
+def test_kmv_dxx_first_columns_are_kmv_dx_bit_for_bit(t, d, kind, with_cols, dtype_name):
+	"""With a j range that is never cut (q <= 256) the d gradient columns and the value column of stpy_kmv_dxx ARE the output of stpy_kmv_dx on
+	the same operands: group 0 of the kernel is the arithmetic of stpy_kmv_dx, statement for statement.  n = 70 is a ragged tile, q = 200 a
+	ragged chunk; every register instantiation, one and two row blocks, coordinates taken directly and through a non-monotone ``cols``."""
+	n, q = 70, 200
+	rng = np.random.RandomState(4100 + 37 * d + t)
+	width = d + 3 if with_cols else d
+	cols = [int(c) for c in rng.permutation(width)[:d]] if with_cols else None
+	a = rng.uniform(-1, 1, size=(n, width)).astype(np.float32).astype(np.float64)
+	b = rng.uniform(-1, 1, size=(q, width)).astype(np.float32).astype(np.float64)
+	b[:9] = a[:9]                                                        # rho == 0 pairs
+	il = (rng.uniform(0.5, 3.0, size=(d,)) / np.sqrt(d)).astype(np.float32).astype(np.float64)
+	V = rng.standard_normal((t, q)).astype(np.float32).astype(np.float64)
+	assert cols is None or sorted(cols) != cols
+	got, first = run(kind, a, b, il, V, cols, dtype_name, want_dx=True)
+	assert first.shape == (t, n, d + 1) and np.all(np.isfinite(first)) and np.any(first[:, :, :d] != 0)
+	assert np.array_equal(got[:, :, :d + 1], first)
