@@ -391,6 +391,61 @@ int stpy_lml_batch(int kind, int dtype, const void* x, int64_t n, int64_t ldx, i
                    void* work, int64_t work_bytes, void* stream);
 
 /*
+ * Local GP experts (LocalExpertsGaussianProcess; Deisenroth and Ng 2015; the reference has no counterpart): E exact GPs on E blocks of the data
+ * under ONE hyper-parameter candidate -- the arithmetic of stpy_lml_batch with the roles of data and candidate exchanged, the factor kept for
+ * prediction.  One kernel term k = kappa phi (SE, MATERN12 / 32 / 52), float64 only (float32: -2); cols, inv_ls (device, d values), kappa as for
+ * stpy_pchol; noise: device, ONE noise std.  The points are gathered by expert: xs (N x ldx), ys (N), offsets: device int32[E + 1], expert e owns
+ * rows offsets[e] .. offsets[e + 1], n_e <= nmax <= stpy_experts_max_n() (512) of them.  nmax is the host's bound on n_e, by which the slices are
+ * sized: an expert that violates it (info[e] = -1), or whose offsets leave [0, N] or decrease (info[e] = -2), is reported and nothing is written
+ * out of bounds.  With NPM = nmax rounded up to 32, `factor` holds E slices of NPM^2 doubles (stpy_experts_factor_bytes, 16-byte aligned, owned
+ * by the caller from the fit to the predictions), `work` of the fit E slices of NPM^2 + 32 NPM doubles, `work` of the prediction 32 NPM doubles
+ * per expert and tile of 32 test points.
+ *
+ * stpy_experts_fit: one workgroup per expert, then one small launch for the totals.  With K_e = kappa phi + noise^2 I = L_e L_e^T on the expert's rows:
+ *   factor slice e     = V_e = L_e^-T, upper triangular, row-major with row stride NP_e = n_e rounded up to 32, bordered by an identity; below
+ *                      the diagonal only the 32 x 32 diagonal blocks and the blocks just below them are written (zeros), the rest is not touched
+ *   alpha[offsets[e]..] = K_e^-1 y_e
+ *   value[e]           = 1/2 y_e^T alpha_e + weight * sum_i log (L_e)_ii
+ *   grad[e*ldg + p]    (grad != NULL; p < np lengthscale slots by pidx, p = np the noise std; ldg >= np + 1) by the formulas of stpy_lml_batch;
+ *                      grad == NULL skips the K_e^-1 and H passes, pidx and np are then unused
+ *   info[e]            = 0, or the 1-based index of the first pivot that is not positive and finite: then value[e] = +inf, alpha_e = 0 and the
+ *                      gradient row is zero; the other experts are unaffected
+ *   total[0]           = sum_e value[e];  total[1 + p] = sum_e grad[e*ldg + p], p <= np (with a gradient; total: np + 2 doubles), in expert order
+ * stpy_experts_predict: one launch, one workgroup per (expert, tile of 32 test points xt: M x ldt).  k* from direct coordinate differences with
+ * the evaluator of the fit (the same bits on a training point);
+ *   mu_e[e*ldm + t]    = k*^T alpha_e
+ *   var_e[e*ldm + t]   = kappa - |L_e^-1 k*|^2, L_e^-1 k* on the fp64 MFMA from the stored factor (a variance of the latent f: no noise term)
+ * an expert with info[e] != 0 (the array the fit wrote) yields mu_e = 0, var_e = kappa.  ldm >= M.
+ * stpy_experts_combine: one thread per test point, sums over experts in expert order; each var_e is first clamped to [kappa 2^-52, kappa];
+ * with c_e = 1 / var_e:   mode 0 PoE: beta_e = 1;  1 gPoE: beta_e = 1 / E;  2 BCM: beta_e = 1;  3 rBCM: beta_e = 1/2 (log kappa - log var_e);
+ *   1 / var = sum beta_e c_e  (+ (1 - E) / kappa for BCM, + (1 - sum beta_e) / kappa for rBCM),   mu = var * sum beta_e c_e mu_e
+ * Every sum has a fixed order, there are no atomics, spin-waits or cooperative grids, no host synchronisation and no allocation: two calls are
+ * bit-identical, and an expert's outputs are bit-identical wherever it sits in whatever batch.
+ * Refused before any HIP call: kind (-1), dtype (-2), a NULL array (-3; cols may be NULL, grad may be NULL, pidx with it), nmax above the cap (-4),
+ * ldx or ldt < d (-5), d < 1 (-6), N / E / M out of range (-9), combine mode (-10), kappa not positive and finite (-11), ldm < M (-13), np < 1
+ * with a gradient (-16), ldg < np + 1 (-19), work_bytes below the query (-20), misalignment (-21), factor_bytes below its query (-22).
+ * E == 0, N == 0 (or M == 0): returns 0, nothing is read or written.
+ */
+int64_t stpy_experts_max_n(void);
+int64_t stpy_experts_factor_bytes(int dtype, int64_t nmax, int64_t E);
+int64_t stpy_experts_fit_workspace_bytes(int dtype, int64_t nmax, int d, int64_t E);
+int stpy_experts_fit(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const void* ys,
+                     const int32_t* offsets, int64_t E, int64_t nmax,
+                     const void* inv_ls, const void* noise, double kappa, double weight,
+                     const int32_t* pidx, int np,
+                     void* factor, int64_t factor_bytes, void* alpha, void* value, void* grad, int64_t ldg, void* total, int32_t* info,
+                     void* work, int64_t work_bytes, void* stream);
+int64_t stpy_experts_predict_workspace_bytes(int dtype, int64_t nmax, int d, int64_t E, int64_t M);
+int stpy_experts_predict(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols,
+                         const int32_t* offsets, int64_t E, int64_t nmax, const void* inv_ls, double kappa,
+                         const void* factor, int64_t factor_bytes, const void* alpha, const int32_t* info,
+                         const void* xt, int64_t M, int64_t ldt,
+                         void* mu_e, void* var_e, int64_t ldm,
+                         void* work, int64_t work_bytes, void* stream);
+int stpy_experts_combine(int mode, int64_t E, int64_t M, const void* mu_e, const void* var_e, int64_t ldm, double kappa,
+                         void* mu, void* var, void* stream);
+
+/*
  * Greedy pivoted partial Cholesky of the kernel matrix K_il = kappa phi(|(x_i - x_l)[cols] o inv_ls|), columns generated on the fly: the landmark
  * choice of NystromFeatures(approx="pivoted") (the reference's nystrom_fea.py has uniform / leverage sampling only).  K is never formed:
  * O(n m) memory, O(n m^2) work.  kind, cols, inv_ls, kappa as for stpy_gram; SE and MATERN12 / 32 / 52 only.  Kernel values come from direct

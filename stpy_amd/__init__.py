@@ -6,6 +6,7 @@ behind stpy's own estimator API.  Module layout mirrors the reference for the pa
     stpy_amd.continuous_processes.gauss_procc.GaussianProcess   (stpy/continuous_processes/gauss_procc.py)
     stpy_amd.continuous_processes.nystrom_fea.NystromFeatures   (stpy/continuous_processes/nystrom_fea.py)
     stpy_amd.continuous_processes.iterative_gp.IterativeGaussianProcess   (no counterpart: matrix-free exact GP)
+    stpy_amd.continuous_processes.local_experts.LocalExpertsGaussianProcess   (no counterpart: committee of local exact GPs)
     stpy_amd.embeddings.embedding.{RFFEmbedding, QuadratureEmbedding, HermiteEmbedding, ...}   (stpy/embeddings/embedding.py)
     stpy_amd.helpers.helper.{interval, cartesian}               (stpy/helpers/helper.py)
 
@@ -17,6 +18,7 @@ from .continuous_processes.gauss_procc import GaussianProcess
 from .embeddings.embedding import Embedding, RFFEmbedding, QuadratureEmbedding, HermiteEmbedding
 from .continuous_processes.nystrom_fea import NystromFeatures, pivoted_cholesky
 from .continuous_processes.iterative_gp import IterativeGaussianProcess, PathwiseSamples
+from .continuous_processes.local_experts import LocalExpertsGaussianProcess
 
 __all__ = ["KernelFunction", "GaussianProcess", "Embedding", "RFFEmbedding", "QuadratureEmbedding", "HermiteEmbedding", "NystromFeatures", "pivoted_cholesky",
-		   "IterativeGaussianProcess", "PathwiseSamples"]
+		   "IterativeGaussianProcess", "PathwiseSamples", "LocalExpertsGaussianProcess"]

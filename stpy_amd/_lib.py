@@ -68,6 +68,15 @@ SIGNATURES = {
 	"stpy_lml_batch_max_n": (_i64, []),
 	"stpy_lml_batch_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_lml_batch": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _dbl, _dbl, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+	"stpy_experts_max_n": (_i64, []),
+	"stpy_experts_factor_bytes": (_i64, [_i32, _i64, _i64]),
+	"stpy_experts_fit_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
+	"stpy_experts_fit": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _dbl, _dbl, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64,
+						 _vp, _vp, _vp, _i64, _vp]),
+	"stpy_experts_predict_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64, _i64]),
+	"stpy_experts_predict": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
+							 _vp, _i64, _vp]),
+	"stpy_experts_combine": (_i32, [_i32, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp]),
 	"stpy_pchol_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_pchol": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _i64, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 	"stpy_kmv_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i64]),
@@ -452,6 +461,57 @@ def lml_batch(kind, x, y, inv_ls, noise, pidx, n_params, kappa, weight, cols=Non
 	_launch("stpy_lml_batch", kind, dtype_code(x.dtype), ptr(x), n, ld(x), d, ptr(cols), ptr(y), B, ptr(inv_ls), ld(inv_ls), ptr(noise),
 			float(kappa), float(weight), ptr(pidx), int(n_params), ptr(value), ptr(grad), ldg, ptr(info), ptr(work), work.numel())
 	return value, grad, info, packed
+
+
+def experts_max_n():
+	"""Largest expert stpy_experts_fit accepts."""
+	return int(load().stpy_experts_max_n())
+
+
+def experts_factor(nmax, E, like):
+	"""The factor buffer of E experts of at most nmax points (bytes; stpy_experts_factor_bytes): written by experts_fit, read by experts_predict."""
+	return _work(max(int(load().stpy_experts_factor_bytes(F64, nmax, E)), 16), like)
+
+
+def experts_fit_workspace(nmax, d, E, like):
+	"""Scratch of stpy_experts_fit (dead after the call; one buffer can serve several launches)."""
+	return _work(max(int(load().stpy_experts_fit_workspace_bytes(F64, nmax, d, E)), 16), like)
+
+
+def experts_fit(kind, xs, ys, offsets, nmax, inv_ls, noise, kappa, weight, factor, alpha, pidx=None, n_params=0, cols=None, work=None):
+	"""E = offsets.numel() - 1 exact GPs on the row blocks offsets[e] .. offsets[e + 1] of xs / ys in one launch, plus one for the totals
+	(stpy_experts_fit in the header).  inv_ls (d,), noise (1,) float64 and offsets (E + 1,) int32 on the device; ``factor`` (experts_factor) and
+	``alpha`` (N,) are written.  With ``pidx`` (d,) int32 the gradient is computed: n_params lengthscale slots, then the noise std.  Returns
+	(value (E,), grad (E, n_params + 1) or None, total (n_params + 2,) or (1,), info (E,) int32, packed): views of ONE device buffer ``packed``
+	(bytes: [total | value | grad | info]), so that a caller fetches all of them with a single copy."""
+	N, d, E = xs.shape[0], _ncols(xs, cols), offsets.numel() - 1
+	ldg = n_params + 1 if pidx is not None else 0
+	nt = n_params + 2 if pidx is not None else 1
+	packed = torch.empty(((nt + E * (1 + ldg)) * 8 + E * 4,), dtype=torch.uint8, device=xs.device)
+	total = packed[:nt * 8].view(torch.float64)
+	value = packed[nt * 8:(nt + E) * 8].view(torch.float64)
+	grad = packed[(nt + E) * 8:(nt + E * (1 + ldg)) * 8].view(torch.float64).view(E, ldg) if pidx is not None else None
+	info = packed[(nt + E * (1 + ldg)) * 8:].view(torch.int32)
+	work = experts_fit_workspace(nmax, d, E, xs) if work is None else work
+	_launch("stpy_experts_fit", kind, dtype_code(xs.dtype), ptr(xs), N, ld(xs), d, ptr(cols), ptr(ys), ptr(offsets), E, int(nmax), ptr(inv_ls), ptr(noise),
+			float(kappa), float(weight), ptr(pidx), int(n_params), ptr(factor), factor.numel(), ptr(alpha), ptr(value), ptr(grad), ldg, ptr(total), ptr(info),
+			ptr(work), work.numel())
+	return value, grad, total, info, packed
+
+
+def experts_predict(kind, xs, offsets, nmax, inv_ls, kappa, factor, alpha, info, xt, mu_e, var_e, cols=None, work=None):
+	"""mu_e[e, t], var_e[e, t] (E x M, row stride ld): every expert's posterior mean and latent variance at the test points xt, one launch
+	(stpy_experts_predict in the header)."""
+	N, d, E, M = xs.shape[0], _ncols(xs, cols), offsets.numel() - 1, xt.shape[0]
+	if work is None:
+		work = _work(max(int(load().stpy_experts_predict_workspace_bytes(F64, int(nmax), d, E, M)), 16), xs)
+	_launch("stpy_experts_predict", kind, dtype_code(xs.dtype), ptr(xs), N, ld(xs), d, ptr(cols), ptr(offsets), E, int(nmax), ptr(inv_ls), float(kappa),
+			ptr(factor), factor.numel(), ptr(alpha), ptr(info), ptr(xt), M, ld(xt), ptr(mu_e), ptr(var_e), ld(mu_e), ptr(work), work.numel())
+
+
+def experts_combine(mode, mu_e, var_e, kappa, mu, var):
+	"""mu, var (M,) from the experts' (E, M) predictions: mode 0 PoE, 1 gPoE, 2 BCM, 3 rBCM (stpy_experts_combine in the header)."""
+	_launch("stpy_experts_combine", int(mode), mu_e.shape[0], mu_e.shape[1], ptr(mu_e), ptr(var_e), ld(mu_e), float(kappa), ptr(mu), ptr(var))
 
 
 def pchol(kind, x, inv_ls, m, cols=None, kappa=1.0, tol=0.0, ldf=None):

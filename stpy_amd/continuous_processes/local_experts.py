@@ -1,0 +1,450 @@
+"""
+LocalExpertsGaussianProcess: a committee of exact local GP experts (Deisenroth and Ng, "Distributed Gaussian Processes", ICML 2015) behind the
+estimator surface of ``GaussianProcess``.  The reference has no counterpart, as ``IterativeGaussianProcess`` has none; this is the third scale
+regime of the package:
+
+    dense factorisation (GaussianProcess)        exact, N <= 131 072 on one GPU
+    matrix-free (IterativeGaussianProcess)       exact, any N, a block solve per 64 test points, a randomised evidence
+    local experts (this class)                   an APPROXIMATION: E = ceil(N / expert_size) independent exact GPs on blocks of at most 512
+                                                 points, trained on the factorised evidence sum_e lml_e with its exact gradient, combined
+                                                 by PoE / gPoE / BCM / rBCM -- a million points, predictions in milliseconds
+
+What runs where
+  per-expert Gram fill, Cholesky, L^-T, alpha, evidence, gradient     stpy_experts_fit      (csrc/experts.hip; one workgroup per expert)
+  per-expert mean and latent variance at the test points              stpy_experts_predict  (one workgroup per expert and 32 test points)
+  combination over experts                                            stpy_experts_combine  (one thread per test point)
+Python partitions (numpy, host), gathers the points by expert (one device index_select), sequences those launches and owns the tensors.
+
+The hyper-parameters are shared by all experts; the kernel is ONE stationary term (SE / Matern 1/2, 3/2, 5/2, isotropic or ARD, on a column
+group or on all columns), float64 only.  Variances are those of the latent f (no noise term), as in the dense class; like every ``mean_std`` /
+``mean_var`` of the package the second return value is a standard deviation.
+
+Out of scope (refused with the reason): input gradients and ``ucb_optimize``, spatial partitions beyond a user-given assignment, appending and
+deleting points, float32, an explicit ``Sigma``, composite kernels, several GPUs.
+"""
+import numpy as np
+import torch
+
+from .. import _lib
+from ..estimator import Estimator, Euclidean
+from ..kernels import KernelFunction
+from .nystrom_fea import _stationary_term
+
+EXPERT_CAP = 512                     # stpy_experts_max_n(): checked against the library at the first fit (the constructor stays on the host)
+COMBINE_MODES = {"poe": 0, "gpoe": 1, "bcm": 2, "rbcm": 3}
+# test points of one predict launch: E * chunk stays at or below this many (mu_e, var_e) elements; the launch's workspace is 8 * 32 * ceil(chunk / 32)
+# * E * (largest expert rounded up to 32) bytes -- 2 GiB at experts of 256 points, 4 GiB at 512
+PREDICT_BUDGET = 1 << 20
+_X_KEYS = ("gamma", "ard_gamma", "kappa", "group", "offset", "nu")
+
+
+def balanced_sizes(n, expert_size):
+	"""Sizes of E = ceil(n / expert_size) pieces of n points that differ by at most one, the larger ones first."""
+	n, expert_size = int(n), int(expert_size)
+	if n <= 0:
+		return np.zeros((0,), dtype=np.int64)
+	E = -(-n // expert_size)
+	base, extra = divmod(n, E)
+	return np.asarray([base + 1] * extra + [base] * (E - extra), dtype=np.int64)
+
+
+def partition_points(n, expert_size, partition="random", seed=0):
+	"""(order, sizes): ``order`` lists the point indices expert by expert, ``sizes[e]`` is the number of points of expert e.  "random": a
+	numpy.random.default_rng(seed) permutation cut into balanced pieces; "contiguous": the given order cut the same way; an integer array /
+	tensor of n expert ids: the points of expert e in their given order, E = largest id + 1."""
+	n = int(n)
+	if isinstance(partition, str):
+		if partition not in ("random", "contiguous"):
+			raise ValueError("LocalExpertsGaussianProcess: partition=%r (\"random\", \"contiguous\" or an integer tensor of expert ids)" % (partition,))
+		sizes = balanced_sizes(n, expert_size)
+		order = np.random.default_rng(int(seed)).permutation(n) if partition == "random" else np.arange(n)
+		return order.astype(np.int64), sizes
+	ids = partition.detach().cpu().numpy() if torch.is_tensor(partition) else np.asarray(partition)
+	if ids.dtype.kind not in "iu":
+		raise ValueError("LocalExpertsGaussianProcess: an explicit partition must be an INTEGER tensor of expert ids, got %s" % ids.dtype)
+	ids = ids.reshape(-1).astype(np.int64)
+	if ids.shape[0] != n:
+		raise ValueError("LocalExpertsGaussianProcess: the partition assigns %d points, the data has %d" % (ids.shape[0], n))
+	if n and ids.min() < 0:
+		raise ValueError("LocalExpertsGaussianProcess: negative expert id %d" % int(ids.min()))
+	sizes = np.bincount(ids).astype(np.int64) if n else np.zeros((0,), dtype=np.int64)
+	return np.argsort(ids, kind="stable").astype(np.int64), sizes
+
+
+class _ExpertsEvidenceFn(torch.autograd.Function):
+	"""Autograd node of LocalExpertsGaussianProcess.log_marginal: ONE stpy_experts_fit launch with a gradient; backward hands out its totals."""
+
+	@staticmethod
+	def forward(ctx, gp, term, weight, params, *tensors):
+		val, ctx.grads = gp._evidence(term, weight, params)
+		return val.clone()
+
+	@staticmethod
+	def backward(ctx, gout):
+		scale = gout.reshape(-1)[0]
+		return (None, None, None, None) + tuple(scale.to(g.device) * g for g in ctx.grads)
+
+
+class LocalExpertsGaussianProcess(Estimator):
+
+	def __init__(self, gamma=1, s=0.001, kappa=1., kernel_name="squared_exponential", d=1, kernel=None, nu=1.5, expert_size=256,
+				 partition="random", partition_seed=0, combine="rbcm", max_size=10000):
+		self.s = s
+		self.d = d
+		self.x = self.y = None
+		self.n = 0
+		self.fitted = False
+		self.back_prop = True
+		if kernel is not None:
+			self.kernel_object = kernel
+			self.d = kernel.d
+		else:
+			self.kernel_object = KernelFunction(kernel_name=kernel_name, gamma=gamma, nu=nu, kappa=kappa, d=d)
+		self.kernel = self.kernel_object.kernel
+		self.expert_size, self.partition, self.partition_seed = int(expert_size), partition, int(partition_seed)
+		self.combine, self.max_size = combine, int(max_size)
+		self.assignment_ = self.offsets_ = None          # host arrays: expert id of every point (given order), row range of every expert (gathered order)
+		self.launches = 0                                # kernel launches of this object so far (a fit is 2, a prediction chunk is 2)
+		self.lml_batch_path = "device"
+		self._sizes, self._order = np.zeros((0,), dtype=np.int64), None
+		self._xs = self._ys = self._offsets = self._factor = self._alpha = self._info = self._hyper = None
+		self._check()
+
+	# ------------------------------------------------------------------ host checks
+	def _check(self):
+		"""Everything that can be refused without the data is refused here, on the host."""
+		try:
+			_stationary_term(self.kernel_object)
+		except NotImplementedError as e:
+			raise NotImplementedError("LocalExpertsGaussianProcess: every expert runs ONE stationary kernel term (SE / Matern / ARD) in one workgroup; "
+									  "composite kernels are not supported (%s)" % e)
+		if not 1 <= self.expert_size <= EXPERT_CAP:
+			raise ValueError("LocalExpertsGaussianProcess: expert_size=%d outside [1, %d] (stpy_experts_max_n: an expert is factorised by one workgroup)"
+							 % (self.expert_size, EXPERT_CAP))
+		if self.combine not in COMBINE_MODES:
+			raise ValueError("LocalExpertsGaussianProcess: combine=%r, one of %s" % (self.combine, ", ".join(repr(k) for k in COMBINE_MODES)))
+		if isinstance(self.partition, str) and self.partition not in ("random", "contiguous"):
+			raise ValueError("LocalExpertsGaussianProcess: partition=%r (\"random\", \"contiguous\" or an integer tensor of expert ids)" % (self.partition,))
+		if self.max_size < 1:
+			raise ValueError("LocalExpertsGaussianProcess: max_size must be positive")
+
+	@staticmethod
+	def _no_grad(xtest):
+		if torch.is_tensor(xtest) and xtest.requires_grad:
+			raise NotImplementedError("LocalExpertsGaussianProcess: input gradients of the combined posterior are not implemented (a follow-up); "
+									  "pass a test tensor without requires_grad")
+
+	def description(self):
+		return self.kernel_object.description() + "\nlambda=" + str(self.s) + "\nlocal experts (%s, expert_size %d, %d experts, partition %s)" % (
+			self.combine, self.expert_size, len(self._sizes), self.partition if isinstance(self.partition, str) else "given")
+
+	@property
+	def experts_info(self):
+		"""E, the experts' sizes, the kernel launches so far and the bytes of the resident factor buffer (host bookkeeping only)."""
+		E = int(len(self._sizes))
+		npm = -(-int(self._sizes.max()) // 32) * 32 if E else 0
+		return {"E": E, "sizes": [int(v) for v in self._sizes], "launches": int(self.launches), "factor_bytes": 8 * E * npm * npm if self.fitted else 0}
+
+	def ucb_optimize(self, *args, **kwargs):
+		raise NotImplementedError("LocalExpertsGaussianProcess.ucb_optimize: needs input gradients of the combined posterior, which are not implemented")
+
+	def add_data_point(self, *args, **kwargs):
+		raise NotImplementedError("LocalExpertsGaussianProcess.add_data_point: appending to a fitted committee is not implemented; refit")
+
+	def remove_data_point(self, *args, **kwargs):
+		raise NotImplementedError("LocalExpertsGaussianProcess.remove_data_point: deleting from a fitted committee is not implemented; refit")
+
+	# ------------------------------------------------------------------ fit
+	def fit(self, x=None, y=None):
+		if x is not None:
+			self.fit_gp(x, y)
+		else:
+			self.fit_gp(self.x, self.y)
+
+	def _check_data(self, x, Sigma=None):
+		if Sigma is not None:
+			raise NotImplementedError("LocalExpertsGaussianProcess: an explicit Sigma couples the experts; the noise is s^2 I")
+		dt = x.dtype if torch.is_tensor(x) else np.asarray(x).dtype
+		if dt in (torch.float32, np.dtype("float32")):
+			raise NotImplementedError("LocalExpertsGaussianProcess: float32 data; the expert kernels are float64 only (a 512-point Cholesky in "
+									  "one workgroup has no fp32 route)")
+
+	def _partition(self, n):
+		order, sizes = partition_points(n, self.expert_size, self.partition, self.partition_seed)
+		over = np.nonzero(sizes > EXPERT_CAP)[0]
+		if over.size:
+			raise ValueError("LocalExpertsGaussianProcess: expert %d has %d points, above the cap of %d (stpy_experts_max_n)"
+							 % (int(over[0]), int(sizes[over[0]]), EXPERT_CAP))
+		return order, sizes
+
+	def fit_gp(self, x, y, Sigma=None):
+		self._check()
+		self._check_data(x, Sigma)
+		n = int(x.shape[0])
+		order, sizes = self._partition(n)          # (host; an oversized expert is refused before anything reaches the device)
+		self.n, self.d = x.shape
+		self.x, self.y = x, y
+		self.fitted = False
+		self._factor = self._alpha = self._info = None
+		offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+		assignment = np.empty(n, dtype=np.int64)
+		assignment[order] = np.repeat(np.arange(len(sizes)), sizes)
+		self.assignment_, self.offsets_, self._sizes, self._order = assignment, offsets, sizes, order
+		if _lib.experts_max_n() < EXPERT_CAP:
+			raise _lib.StpyHipError("libstpy_hip.so accepts experts of %d points, the package expects %d" % (_lib.experts_max_n(), EXPERT_CAP))
+		xd = _lib.to_device(x, torch.float64)
+		yd = _lib.to_device(y, torch.float64).reshape(-1)
+		idx = torch.from_numpy(order).to(xd.device)
+		self._xs, self._ys = xd.index_select(0, idx).contiguous(), yd.index_select(0, idx).contiguous()
+		self._offsets = torch.from_numpy(offsets.astype(np.int32)).to(xd.device)
+		if n == 0:
+			return None
+		term = _stationary_term(self.kernel_object)
+		nmax, E = int(sizes.max()), len(sizes)
+		factor = _lib.experts_factor(nmax, E, xd)
+		alpha = torch.empty((n,), dtype=torch.float64, device=xd.device)
+		cols, inv_ls, noise = self._operands(term, float(self.s))
+		_, _, _, info, packed = _lib.experts_fit(term['kind'], self._xs, self._ys, self._offsets, nmax, inv_ls, noise, term['kappa'], 1.0, factor, alpha, cols=cols)
+		self.launches += 2
+		self._raise_failed(packed.cpu().numpy()[-4 * E:].view(np.int32), "fit_gp")          # the one read-back of a fit (waits for the launch)
+		self._factor, self._alpha, self._info = factor, alpha, info
+		self._hyper = (term['kind'], float(term['kappa']), cols, inv_ls, nmax)
+		self.fitted = True
+		return None
+
+	def _operands(self, term, s):
+		xs = self._xs
+		cols, inv_ls = self.kernel_object._term_operands(term, xs, xs.dtype, xs.device)
+		return cols, inv_ls, torch.tensor([float(s)], dtype=torch.float64).to(xs.device)
+
+	@staticmethod
+	def _raise_failed(info, what):
+		bad = np.nonzero(info)[0]
+		if bad.size:
+			e, piv = int(bad[0]), int(info[bad[0]])
+			if piv < 0:
+				raise _lib.StpyHipError("LocalExpertsGaussianProcess.%s: expert %d does not fit the sizes the launch was made for (info %d)" % (what, e, piv))
+			raise torch.linalg.LinAlgError("LocalExpertsGaussianProcess.%s: expert %d: the leading minor of order %d of K_e + s^2 I is not positive definite "
+										   "(%d of %d experts failed)" % (what, e, piv, int(bad.size), int(info.shape[0])))
+
+	@property
+	def A(self):
+		"""The experts' K_e^-1 y_e, in the order of the data, (N, 1)."""
+		if self._alpha is None:
+			return None
+		out = torch.empty_like(self._alpha)
+		out[torch.from_numpy(self._order).to(out.device)] = self._alpha
+		return _lib.like_input(out.reshape(-1, 1), self.x)
+
+	# ------------------------------------------------------------------ prediction
+	def _prior(self, xtest):
+		term = _stationary_term(self.kernel_object)
+		m = int(xtest.shape[0])
+		dt = xtest.dtype if torch.is_tensor(xtest) and xtest.dtype.is_floating_point else torch.float64
+		dev = xtest.device if torch.is_tensor(xtest) else "cpu"
+		return torch.zeros((m, 1), dtype=dt, device=dev), torch.full((m, 1), float(np.sqrt(term['kappa'])), dtype=dt, device=dev)
+
+	def _chunks(self, m):
+		E = max(len(self._sizes), 1)
+		step = max(1, min(self.max_size, PREDICT_BUDGET // E))
+		return [(a, min(a + step, m)) for a in range(0, m, step)]
+
+	def _experts_device(self, xt):
+		"""(mu_e, var_e), (E, M) device tensors: one stpy_experts_predict launch per chunk of test points."""
+		kind, kappa, cols, inv_ls, nmax = self._hyper
+		E, m = len(self._sizes), xt.shape[0]
+		mu_e = torch.empty((E, m), dtype=torch.float64, device=xt.device)
+		var_e = torch.empty((E, m), dtype=torch.float64, device=xt.device)
+		for a, b in self._chunks(m):
+			_lib.experts_predict(kind, self._xs, self._offsets, nmax, inv_ls, kappa, self._factor, self._alpha, self._info, xt[a:b], mu_e[:, a:b], var_e[:, a:b], cols=cols)
+			self.launches += 1
+		return mu_e, var_e
+
+	def expert_mean_var(self, xtest):
+		"""Every expert's posterior mean and latent VARIANCE at the test points, two (E, M) tensors placed like ``xtest`` (diagnostics)."""
+		self._no_grad(xtest)
+		if not self.fitted:
+			raise AttributeError("LocalExpertsGaussianProcess.expert_mean_var needs a fitted object: call fit_gp first")
+		mu_e, var_e = self._experts_device(_lib.to_device(xtest, torch.float64))
+		return _lib.like_input(mu_e, xtest), _lib.like_input(var_e, xtest)
+
+	def _mean_var_device(self, xt):
+		kind, kappa, cols, inv_ls, nmax = self._hyper
+		E, m = len(self._sizes), xt.shape[0]
+		mu = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		var = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		for a, b in self._chunks(m):
+			mu_e = torch.empty((E, b - a), dtype=torch.float64, device=xt.device)
+			var_e = torch.empty((E, b - a), dtype=torch.float64, device=xt.device)
+			_lib.experts_predict(kind, self._xs, self._offsets, nmax, inv_ls, kappa, self._factor, self._alpha, self._info, xt[a:b], mu_e, var_e, cols=cols)
+			_lib.experts_combine(COMBINE_MODES[self.combine], mu_e, var_e, kappa, mu[a:b], var[a:b])
+			self.launches += 2
+		return mu, var
+
+	def mean_std(self, xtest):
+		"""Combined posterior mean and standard deviation of the latent f, (M, 1) each, placed like ``xtest``; the prior before a fit."""
+		self._no_grad(xtest)
+		if not self.fitted:
+			return self._prior(xtest)
+		xt = _lib.to_device(xtest, torch.float64)
+		mu, var = self._mean_var_device(xt)
+		sd = torch.empty_like(var)
+		if xt.shape[0] > 0:
+			_lib.predict_finish(sumsq=torch.zeros_like(var), kdiag=var, scale=0.0, sigma=sd)
+		return _lib.like_input(mu.reshape(-1, 1), xtest), _lib.like_input(sd.reshape(-1, 1), xtest)
+
+	mean_var = mean_std
+
+	def mean(self, xtest):
+		return self.mean_std(xtest)[0]
+
+	def lcb(self, xtest):
+		mu, s = self.mean_std(xtest)
+		return mu - 2 * s
+
+	def ucb(self, xtest):
+		mu, s = self.mean_std(xtest)
+		return mu + 2 * s
+
+	# ------------------------------------------------------------------ the factorised evidence
+	def _check_overrides(self, kernel, X):
+		"""Host refusals of log_marginal; returns (X, the one stationary term the overrides resolve to)."""
+		X = {} if X is None else X
+		if kernel is not self.kernel_object:
+			_stationary_term(kernel)
+		for key, item in X.items():
+			if str(key) != "0" or not isinstance(item, dict):
+				raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: overrides for kernel item %r; the experts' kernel has ONE item, '0'" % (key,))
+			for name, v in item.items():
+				if name not in _X_KEYS:
+					raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: override %r is not a lengthscale of a single stationary term "
+											  "(supported: 'gamma' / 'ard_gamma')" % (name,))
+				if name not in ("gamma", "ard_gamma") and torch.is_tensor(v) and v.requires_grad:
+					raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: no gradient with respect to %r (lengthscales and the noise only)" % name)
+		items = kernel._chain(X if X else None)
+		if len(items) != 1 or len(items[0]['terms']) != 1:
+			raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: the overrides resolve to %d items; ONE stationary term is supported" % len(items))
+		term = items[0]['terms'][0]
+		if term['premap'] is not None or term['pname'] is None or term['kind'] not in (_lib.K_SE, _lib.K_MATERN12, _lib.K_MATERN32, _lib.K_MATERN52):
+			raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: the %s kernel is not one stationary term" % kernel._term_name(term))
+		return X, term
+
+	def _grad_params(self, X):
+		"""(key, name, tensor) for every hyper-parameter tensor that asks for a gradient (the convention of GaussianProcess)."""
+		out = []
+		for key in sorted(X.keys()):
+			for name in ("gamma", "ard_gamma"):
+				v = X[key].get(name)
+				if torch.is_tensor(v) and v.requires_grad:
+					out.append((key, name, v))
+		if torch.is_tensor(self.s) and self.s.requires_grad:
+			out.append(("likelihood", "sigma", self.s))
+		return out
+
+	def _need_data(self, what):
+		if self._xs is None or self._xs.shape[0] == 0:
+			raise AttributeError("LocalExpertsGaussianProcess.%s needs data and a partition: call fit_gp first" % what)
+
+	def _launch_evidence(self, term, weight, s, n_params, scratch):
+		"""One stpy_experts_fit launch with a gradient on the current partition, into factor / alpha / workspace buffers of its own (the
+		resident factor stays); returns the packed device results, unread."""
+		xs = self._xs
+		nmax, E = int(self._sizes.max()), len(self._sizes)
+		if "factor" not in scratch:
+			scratch["factor"] = _lib.experts_factor(nmax, E, xs)
+			scratch["alpha"] = torch.empty((xs.shape[0],), dtype=torch.float64, device=xs.device)
+			scratch["work"] = _lib.experts_fit_workspace(nmax, len(term['group']), E, xs)
+		cols, inv_ls, noise = self._operands(term, s)
+		pidx = self.kernel_object._term_param_slots(term, xs.device)
+		w = float(weight.item()) if torch.is_tensor(weight) else float(weight)
+		packed = _lib.experts_fit(term['kind'], xs, self._ys, self._offsets, nmax, inv_ls, noise, term['kappa'], w, scratch["factor"], scratch["alpha"],
+								  pidx=pidx, n_params=n_params, cols=cols, work=scratch["work"])[4]
+		self.launches += 2
+		return packed
+
+	@staticmethod
+	def _n_params(term, given):
+		return max(int(np.prod(tuple(given.shape))) if given is not None and torch.is_tensor(given) and given.dim() > 0 else 1, max(term['pidx']) + 1)
+
+	def _evidence(self, term, weight, params):
+		"""(value (1, 1) placed like the data, [gradient per entry of params]) from one launch and one read-back."""
+		E = len(self._sizes)
+		given = next((t for (key, name, t) in params if key != "likelihood"), None)
+		n_params = self._n_params(term, given)
+		out = self._launch_evidence(term, weight, float(self.s), n_params, {}).cpu().numpy()
+		self._raise_failed(out[-4 * E:].view(np.int32), "log_marginal")
+		total = out[:(n_params + 2) * 8].view(np.float64)
+		grads = []
+		for (key, name, t) in params:
+			if key == "likelihood":
+				g = torch.full(t.shape if t.dim() > 0 else (), float(total[1 + n_params]), dtype=torch.float64)
+			else:
+				if term['pname'] != name:
+					raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: the kernel has no '%s' lengthscale" % name)
+				g = torch.from_numpy(total[1:1 + n_params].copy()).reshape(t.shape if t.dim() > 0 else ())
+			grads.append(g.to(device=t.device, dtype=t.dtype))
+		val = torch.full((1, 1), float(total[0]), dtype=torch.float64)
+		return (val.to(self.x.device) if torch.is_tensor(self.x) and self.x.is_cuda else val), grads
+
+	def log_marginal(self, kernel, X, weight):
+		"""The factorised evidence sum_e [1/2 y_e^T (K_e + s^2 I)^-1 y_e + 1/2 weight log det(K_e + s^2 I)] on the current partition, shape (1, 1):
+		the sign, shape and omitted n/2 log 2 pi constant of GaussianProcess.log_marginal.  ``X``: overrides of the single kernel item,
+		{'0': {'gamma' | 'ard_gamma': tensor}}.  If a lengthscale tensor in ``X`` or ``self.s`` requires grad the result carries an autograd node
+		whose backward is the exact gradient, summed over the experts in expert order on the device.  The resident factor is left untouched."""
+		X, term = self._check_overrides(kernel, X)
+		self._need_data("log_marginal")
+		params = self._grad_params(X)
+		if params:
+			return _ExpertsEvidenceFn.apply(self, term, weight, params, *[t for (_, _, t) in params])
+		return self._evidence(term, weight, [])[0]
+
+	def log_marginal_batch(self, kernel, Xs, weight, s=None):
+		"""``log_marginal`` and its gradient for B candidates: one stpy_experts_fit launch per candidate, enqueued back to back into shared
+		scratch, one read-back each at the end.  Returns what Estimator.optimize_params_general expects: (values (B,), grads), ``grads[b]`` =
+		{'0': {parameter name: tensor}} plus {'likelihood': {'sigma': ...}} when ``s`` is given.  A candidate with a failed expert gets +inf and
+		zero gradients, no exception."""
+		self._need_data("log_marginal_batch")
+		if s is not None and len(s) != len(Xs):
+			raise ValueError("log_marginal_batch: %d noise levels for %d candidates" % (len(s), len(Xs)))
+		E, scratch, pending = len(self._sizes), {}, []
+		for b, X in enumerate(Xs):
+			X, term = self._check_overrides(kernel, X)
+			given = X.get('0', {}).get(term['pname']) if X else None
+			given = torch.as_tensor(given) if given is not None else None
+			n_params = self._n_params(term, given)
+			shape = tuple(given.shape) if given is not None and given.dim() > 0 else (n_params,)
+			pending.append((term, n_params, shape, self._launch_evidence(term, weight, float(self.s if s is None else s[b]), n_params, scratch)))
+		values, grads = [], []
+		for term, n_params, shape, packed in pending:
+			out = packed.cpu().numpy()
+			total = out[:(n_params + 2) * 8].view(np.float64)
+			ok = not np.any(out[-4 * E:].view(np.int32)) and np.isfinite(total[0])
+			values.append(float(total[0]) if ok else float("inf"))
+			g = {'0': {term['pname']: (torch.from_numpy(total[1:1 + n_params].copy()) if ok else torch.zeros(n_params, dtype=torch.float64)).reshape(shape)}}
+			if s is not None:
+				g['likelihood'] = {'sigma': torch.tensor([float(total[1 + n_params]) if ok else 0.0], dtype=torch.float64)}
+			grads.append(g)
+		self.lml_batch_path = "device"
+		values = torch.tensor(values, dtype=torch.float64)
+		return (values.to(self.x.device) if torch.is_tensor(self.x) and self.x.is_cuda else values), grads
+
+	def optimize_params(self, type='bandwidth', restarts=10, regularizer=None, maxiter=1000, mingradnorm=1e-4, verbose=False, optimizer="pymanopt",
+						scale=1., weight=1., save=False, save_name='model.np', init_func=None, bounds=None, parallel=False, cores=None):
+		"""GaussianProcess.optimize_params for ``type`` in {"bandwidth", "bandwidth+noise"} with the factorised evidence for the objective: the
+		same parameter dictionary through Estimator.optimize_params_general, which writes the best point back and refits."""
+		if type not in ("bandwidth", "bandwidth+noise"):
+			raise NotImplementedError("LocalExpertsGaussianProcess.optimize_params(type='%s'): 'bandwidth' and 'bandwidth+noise' only" % type)
+		if regularizer is not None:
+			raise NotImplementedError("LocalExpertsGaussianProcess.optimize_params: no regularizer")
+		self._need_data("optimize_params")
+		params = {}
+		for key, dict2 in self.kernel_object.params_dict.items():
+			if 'gamma' in dict2.keys():
+				params[key] = {'gamma': (init_func, Euclidean(1), bounds)}
+			elif 'ard_gamma' in dict2.keys():
+				params[key] = {'ard_gamma': (init_func, Euclidean(len(dict2['group'])), bounds)}
+		if type == "bandwidth+noise":
+			s0 = self.s
+			params['likelihood'] = {'sigma': ((lambda k: s0), Euclidean(1), None)}
+		return self.optimize_params_general(params=params, restarts=restarts, optimizer=optimizer, maxiter=maxiter, mingradnorm=mingradnorm,
+											verbose=verbose, scale=scale, weight=weight, save=save, save_name=save_name, parallel=parallel, cores=cores)

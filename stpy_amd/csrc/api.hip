@@ -619,3 +619,6 @@ int stpy_profile_read_union(int tagmask, double* busy_ms, double* total_flops, i
 
 // stpy_kmv_dxx and its workspace query: values, query-point gradients and Hessians of matrix-free kernel sums (kmvdxx.hip), compiled here for the same reason.
 #include "kmvdxx.hip"
+
+// stpy_experts_fit / _predict / _combine and their queries: the local GP experts (experts.hip), compiled here for the same reason.
+#include "experts.hip"

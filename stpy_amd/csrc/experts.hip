@@ -1,0 +1,516 @@
+// Local GP experts (stpy_experts_fit / _predict / _combine; LocalExpertsGaussianProcess): E exact GPs on E different blocks of the data under ONE
+// hyper-parameter candidate, the mirror image of the batched evidence (reduce.hip: B candidates on the same data), from the same one-workgroup
+// building blocks (lb_block.h).
+//
+// Layout.  The points are gathered by expert: xs (N x ldx), ys (N), offsets[E + 1]; expert e owns the rows offsets[e] .. offsets[e + 1], n_e of
+// them, NP_e = n_e rounded up to 32.  With NPM = nmax rounded up to 32:
+//   factor  E slices of NPM^2 doubles: V_e = L_e^-T, upper triangular, row-major with row stride NP_e, bordered by an identity, the blocks just
+//           below its block diagonal stored as zero (what lies further below is never written and never read).  Kept by the caller from the
+//           fit to the predictions.
+//   work    fit: E slices of NPM^2 + 32 NPM doubles (A_e, then the inverse diagonal blocks); dead after the call.
+//           predict: one slice of 32 NPM doubles per (expert, test tile): the k* tile, TRANSPOSED (32 test points x NP_e).
+// The fit kernel is lml_batch_kernel with the expert's rows in place of the candidate's hyper-parameters, V in the factor buffer instead of the
+// workspace, alpha stored, and the K^-1 / H passes skipped without a gradient.  It is a kernel of its own so that stpy_lml_batch keeps its code.
+//
+// Prediction, per (expert, tile of 32 test points): k* from direct differences with the evaluator of the fit (ex_r2 + lb_phi: the same bits on a
+// training point), mu = k*^T alpha by one wave per test point, v = L^-1 k* = V^T k* on the fp64 MFMA 64 rows at a time -- lb_panel's loop with
+// the A tile fetched TRANSPOSED from V (V[k][i] is (L^-1)[i][k]; lanes run along i, so the global reads stay coalesced) -- and the column sums of
+// v o v straight from the accumulators: v is never stored.  The tile is 32 because that is the width of the panel product (two 16-column MFMA
+// halves share one A fragment); 64 columns would run the product twice over the same V for half as many k* slices, and the slice, 128 KB at
+// n_e = 512, is what bounds how many test points one launch can take.
+// Every sum has a fixed order and no workgroup reads what another wrote: an expert's outputs are bit-identical wherever it sits in whatever batch.
+// Compiled inside api.hip (which includes this file, as it includes pchol.hip and the kmv family; it also compiles on its own, as the resource
+// test does) and NOT beside lml_batch_kernel in reduce.hip: more kernels in that translation unit change its LDS layout and with it its instructions.
+// Barriers: as in lml_batch_kernel, every __syncthreads() is reached by the whole workgroup; the early exits test workgroup-uniform words.
+#include "common.h"
+#include "lb_block.h"
+
+namespace stpy {
+
+constexpr int EX_TILE = 32;          // test points per workgroup of the prediction
+
+struct ExpertsFitArgs {
+	const double* xs; int64_t N, ldx; int d; const int32_t* cols; const double* ys; const int32_t* offsets; int nmax;
+	const double* inv_ls; const double* noise; double kappa, weight; const int32_t* pidx; int np;
+	double* factor; int64_t fslice; double* alpha; double* value; double* grad; int64_t ldg; int32_t* info;
+	double* work; int64_t wslice;          // doubles per expert
+	int kind;
+};
+
+struct ExpertsPredictArgs {
+	const double* xs; int64_t N, ldx; int d; const int32_t* cols; const int32_t* offsets; int nmax;
+	const double* inv_ls; double kappa; const double* factor; int64_t fslice; const double* alpha; const int32_t* info;
+	const double* xt; int64_t M, ldt; double* mu_e; double* var_e; int64_t ldm;
+	double* work; int64_t wslice; int ntiles;
+	int kind;
+};
+
+inline int64_t experts_npm(int64_t nmax) { return (nmax + 31) / 32 * 32; }
+inline int64_t experts_factor_slice(int64_t nmax) { return experts_npm(nmax) * experts_npm(nmax); }
+inline int64_t experts_fit_slice(int64_t nmax) { return experts_npm(nmax) * experts_npm(nmax) + 32 * experts_npm(nmax); }
+inline int64_t experts_predict_slice(int64_t nmax) { return EX_TILE * experts_npm(nmax); }
+
+// scaled squared distance of two rows from direct coordinate differences (the sum of lml_batch_kernel's lb_r2)
+__device__ __forceinline__ double ex_r2(const double* __restrict__ xi, const double* __restrict__ xj, const int32_t* __restrict__ cols,
+                                        const double* __restrict__ il, int d)
+{
+	double s = 0.0;
+	for (int k = 0; k < d; ++k) {
+		const int c = cols ? cols[k] : k;
+		const double u = (xi[c] - xj[c]) * il[k];
+		s = fma(u, u, s);
+	}
+	return s;
+}
+
+// (__launch_bounds__(256) and not (256, 2): the kernel needs about 200 VGPRs either way, two workgroups per CU, but under the tighter bound the
+// allocator parks one of the VGPRs that hold spilled SGPRs in scratch)
+template <bool GRAD>
+__global__ __launch_bounds__(256)
+void experts_fit_kernel(ExpertsFitArgs p)
+{
+	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
+	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
+	__shared__ double zs[LB_MAX_N], al[LB_MAX_N], red[4];
+	__shared__ int s_info;
+	const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int lo = p.offsets[b], hi = p.offsets[b + 1];
+	constexpr bool have_grad = GRAD;          // (without a gradient: no K^-1, no H, a kernel of its own)
+	double* grow = have_grad ? p.grad + (int64_t)b * p.ldg : nullptr;
+	if (tid == 0) {
+		s_info = 0;
+		if (have_grad)
+			for (int k = 0; k <= p.np; ++k) grow[k] = 0.0;
+	}
+	if (lo < 0 || hi < lo || hi > p.N || hi - lo > p.nmax) {          // (the same words for every thread) nothing of this expert is sized for: report it
+		const bool inside = lo >= 0 && hi >= lo && hi <= p.N;
+		if (inside)
+			for (int i = lo + tid; i < hi; i += 256) p.alpha[i] = 0.0;
+		if (tid == 0) {
+			p.value[b] = __builtin_huge_val();
+			p.info[b] = inside ? -1 : -2;
+		}
+		return;
+	}
+	const int n = hi - lo, NP = (n + 31) & ~31, nblk = NP >> 5, ld = NP;
+	const double* x = p.xs + (int64_t)lo * p.ldx;
+	const double* y = p.ys + lo;
+	double* A = p.work + (int64_t)b * p.wslice;
+	double* dinv = A + (int64_t)NP * NP;
+	double* V = p.factor + (int64_t)b * p.fslice;
+	const double* il = p.inv_ls;
+	const double sd = p.noise[0], s2 = sd * sd, kappa = p.kappa, wgt = p.weight;
+	const int ec = tid & 31, er = tid >> 5;              // entry of a 32 x 32 block in the elementwise passes: column, first of 4 rows (8 apart)
+
+	// ---- 1. lower blocks of K (whole diagonal blocks), identity border; the blocks of V just below its diagonal are stored as zero
+	for (int bi = 0; bi < nblk; ++bi)
+		for (int bj = 0; bj <= bi; ++bj)
+#pragma unroll
+			for (int q = 0; q < 4; ++q) {
+				const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
+				double v = i == j ? 1.0 : 0.0;
+				if (i < n && j < n) v = kappa * lb_phi(p.kind, ex_r2(x + (int64_t)i * p.ldx, x + (int64_t)j * p.ldx, p.cols, il, p.d)) + (i == j ? s2 : 0.0);
+				A[(int64_t)i * ld + j] = v;
+				if (bi == bj + 1) V[(int64_t)i * ld + j] = 0.0;
+			}
+
+	// ---- 2. Cholesky
+	for (int bk = 0; bk < nblk; ++bk) {
+		const int j0 = 32 * bk;
+		double* Ajj = A + (int64_t)j0 * ld + j0;
+		if (bk > 0) lb_panel<1>(Ajj, ld, A + (int64_t)j0 * ld, ld, A + (int64_t)j0 * ld, ld, NP - j0, j0, -1, As, Bs);
+		__syncthreads();
+		if (wave == 0) {
+			int bad;
+			[[clang::always_inline]] bad = lb_diag(A, V, ld, j0, dinv + bk * 1024, As);          // (two instances = two callers: the inliner would leave a call, and with it a stack)
+			if (bad != 0 && lane == 0) s_info = j0 + bad;
+		}
+		__syncthreads();
+		if (s_info != 0) {          // (the same word for every thread: the workgroup leaves as a whole)
+			for (int i = tid; i < n; i += 256) p.alpha[lo + i] = 0.0;
+			if (tid == 0) {
+				p.value[b] = __builtin_huge_val();
+				p.info[b] = s_info;
+			}
+			return;
+		}
+		if (j0 + 32 < NP) lb_panel<0>(Ajj + (int64_t)32 * ld, ld, Ajj + (int64_t)32 * ld, ld, dinv + bk * 1024, 32, NP - j0 - 32, 32, -1, As, Bs);
+	}
+	__syncthreads();
+	double logdiag = 0.0;
+	for (int i = tid; i < n; i += 256) logdiag += log(A[(int64_t)i * ld + i]);
+	logdiag = lb_block_sum(logdiag, red);
+
+	// ---- 3. V = L^-T: block column I from the finished columns left of it, V[0:i0, I] = -(V[0:i0, 0:i0] L[I, 0:i0]^T) dinv_I^T
+	for (int bk = 1; bk < nblk; ++bk) {
+		const int i0 = 32 * bk;
+		lb_panel<0>(V + i0, ld, V, ld, A + (int64_t)i0 * ld, ld, i0, i0, 0, As, Bs);
+		lb_panel<2>(V + i0, ld, V + i0, ld, dinv + bk * 1024, 32, i0, 32, -1, As, Bs);
+	}
+	__syncthreads();
+
+	// ---- 4. z = W y (z_i = sum_{k <= i} V[k][i] y_k), alpha = W^T z (alpha_j = sum_{k >= j} V[j][k] z_k)
+	for (int i = tid; i < NP; i += 256) {
+		const int kend = min(32 * (i / 32 + 1), n);
+		double z = 0.0;
+#pragma unroll 8
+		for (int k = 0; k < kend; ++k) z = fma(V[(int64_t)k * ld + i], y[k], z);
+		zs[i] = i < n ? z : 0.0;
+	}
+	__syncthreads();
+	for (int j = wave; j < n; j += 4) {
+		const double* vr = V + (int64_t)j * ld;
+		double s = 0.0;
+		for (int k = 32 * (j / 32) + lane; k < NP; k += 64) s = fma(vr[k], zs[k], s);
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+		if (lane == 0) al[j] = s;
+	}
+	__syncthreads();
+	double quad = 0.0, aa = 0.0;
+	for (int i = tid; i < n; i += 256) {
+		quad = fma(zs[i], zs[i], quad);
+		aa = fma(al[i], al[i], aa);
+		p.alpha[lo + i] = al[i];
+	}
+	quad = lb_block_sum(quad, red);
+	if (!have_grad) {
+		if (tid == 0) {
+			p.value[b] = 0.5 * quad + wgt * logdiag;
+			p.info[b] = 0;
+		}
+		return;
+	}
+	aa = lb_block_sum(aa, red);
+
+	// ---- K^-1 = V V^T over A's lower blocks (L is no longer needed), then H = (w K^-1 - alpha alpha^T) o kappa F below the diagonal
+	for (int bk = 0; bk < nblk; ++bk) {
+		const int j0 = 32 * bk;
+		lb_panel<0>(A + (int64_t)j0 * ld + j0, ld, V + (int64_t)j0 * ld, ld, V + (int64_t)j0 * ld, ld, NP - j0, NP, j0, As, Bs);
+	}
+	__syncthreads();
+	double tr = 0.0;
+	for (int bi = 0; bi < nblk; ++bi)
+		for (int bj = 0; bj <= bi; ++bj)
+#pragma unroll
+			for (int q = 0; q < 4; ++q) {
+				const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
+				double h = 0.0;
+				if (i < n && j <= i) {
+					const double kv = A[(int64_t)i * ld + j];
+					if (i == j) tr += kv;
+					else h = (wgt * kv - al[i] * al[j]) * kappa * lb_dfactor(p.kind, ex_r2(x + (int64_t)i * p.ldx, x + (int64_t)j * p.ldx, p.cols, il, p.d));
+				}
+				A[(int64_t)i * ld + j] = h;
+			}
+	tr = lb_block_sum(tr, red);          // (its barriers also order the H stores before the passes below: each entry is re-read by the thread that wrote it anyway)
+
+	// ---- lengthscale sums: 1/2 sum_ij H_ij u_m^2 / l_m = inv_ls_m sum_{i > j} H_ij u_m^2, four coordinates per pass over H
+	for (int m0 = 0; m0 < p.d; m0 += 4) {
+		double sm[4] = {0.0, 0.0, 0.0, 0.0};
+		for (int bi = 0; bi < nblk; ++bi)
+			for (int bj = 0; bj <= bi; ++bj)
+#pragma unroll
+				for (int q = 0; q < 4; ++q) {
+					const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
+					if (i < n && j < i) {
+						const double h = A[(int64_t)i * ld + j];
+						const double* xi = x + (int64_t)i * p.ldx;
+						const double* xj = x + (int64_t)j * p.ldx;
+#pragma unroll
+						for (int e = 0; e < 4; ++e)
+							if (m0 + e < p.d) {
+								const int c = p.cols ? p.cols[m0 + e] : m0 + e;
+								const double u = (xi[c] - xj[c]) * il[m0 + e];
+								sm[e] = fma(h, u * u, sm[e]);
+							}
+					}
+				}
+#pragma unroll
+		for (int e = 0; e < 4; ++e) sm[e] = lb_block_sum(sm[e], red);
+		if (tid == 0) {
+#pragma unroll
+			for (int e = 0; e < 4; ++e)
+				if (m0 + e < p.d) {
+					const int pi = p.pidx[m0 + e];
+					if (pi >= 0 && pi < p.np) grow[pi] += sm[e] * il[m0 + e];
+				}
+		}
+	}
+	if (tid == 0) {
+		p.value[b] = 0.5 * quad + wgt * logdiag;
+		grow[p.np] = sd * (wgt * tr - aa);
+		p.info[b] = 0;
+	}
+}
+
+// total[0] = sum_e value[e], total[1 + q] = sum_e grad[e*ldg + q] (q <= np; only with a gradient): one workgroup, thread q owns output q and adds
+// in expert order
+__global__ __launch_bounds__(64)
+void experts_total_kernel(const double* value, const double* grad, int64_t ldg, int np, int64_t E, double* total)
+{
+	const int nout = grad ? np + 2 : 1;
+	for (int q = threadIdx.x; q < nout; q += 64) {
+		double s = 0.0;
+		if (q == 0)
+			for (int64_t e = 0; e < E; ++e) s += value[e];
+		else
+			for (int64_t e = 0; e < E; ++e) s += grad[e * ldg + q - 1];
+		total[q] = s;
+	}
+}
+
+__global__ __launch_bounds__(256, 2)
+void experts_predict_kernel(ExpertsPredictArgs p)
+{
+	typedef Mfma<double>::v4 v4;
+	typedef Mfma<double>::v2 v2;
+	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
+	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
+	__shared__ double ssq[4][EX_TILE];
+	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const int e = blockIdx.x / p.ntiles, tile = blockIdx.x - e * p.ntiles;
+	const int64_t t0 = (int64_t)tile * EX_TILE;
+	const int mt = (int)min((int64_t)EX_TILE, p.M - t0);
+	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
+	double* mu = p.mu_e + (int64_t)e * p.ldm + t0;
+	double* var = p.var_e + (int64_t)e * p.ldm + t0;
+	if (p.info[e] != 0 || lo < 0 || hi < lo || hi > p.N || hi - lo > p.nmax) {          // (workgroup-uniform) an expert without a factor: the prior
+		if (tid < mt) {
+			mu[tid] = 0.0;
+			var[tid] = p.kappa;
+		}
+		return;
+	}
+	const int n = (int)(hi - lo), NP = (n + 31) & ~31, ld = NP;
+	const double* x = p.xs + lo * p.ldx;
+	const double* al = p.alpha + lo;
+	const double* V = p.factor + (int64_t)e * p.fslice;
+	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;          // KT[t][k] = k(xt_{t0 + t}, x_k), zero for t >= mt and k >= n
+	const double* il = p.inv_ls;
+
+	// ---- 1. the k* tile
+	for (int k = tid; k < NP; k += 256) {
+		const double* xk = x + (int64_t)k * p.ldx;
+		for (int t = 0; t < EX_TILE; ++t) {
+			double v = 0.0;
+			if (k < n && t < mt) v = p.kappa * lb_phi(p.kind, ex_r2(xk, p.xt + (t0 + t) * p.ldt, p.cols, il, p.d));
+			KT[(int64_t)t * ld + k] = v;
+		}
+	}
+	__syncthreads();
+
+	// ---- 2. mu_t = sum_k k*_kt alpha_k: one wave per test point, lanes strided over k, shuffle tree
+	for (int t = w; t < mt; t += 4) {
+		const double* kr = KT + (int64_t)t * ld;
+		double s = 0.0;
+		for (int k = lane; k < n; k += 64) s = fma(kr[k], al[k], s);
+#pragma unroll
+		for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+		if (lane == 0) mu[t] = s;
+	}
+
+	// ---- 3. v = L^-1 k* = V^T k*, 64 rows per round, and the column sums of v o v from the accumulators.  Row i of L^-1 ends at column i: the round
+	// that starts at row r0 runs over k < r0 + 64 (the block of V below the diagonal block of the round's first 32 rows is stored as zero).
+	const int ar = tid & 63, ak = (tid >> 6) * 8;         // A tile (64 rows x 32 k), fetched transposed: this thread's row and the first of its 8 k
+	const int br = tid >> 3, bk = (tid & 7) * 4;          // B tile (32 test points x 32 k): row, first of 4 k
+	const int fr = lane & 15, fk = lane >> 4;             // MFMA operand fragment
+	double q0 = 0.0, q1 = 0.0;
+	for (int r0 = 0; r0 < NP; r0 += 64) {
+		const int kend = min(r0 + 64, NP);
+		const bool arow = r0 + ar < NP;
+		const double* ap = V + (int64_t)ak * ld + r0 + ar;
+		const double* bp = KT + (int64_t)br * ld + bk;
+		double ra[8];
+		v2 rb[2];
+		auto fetch = [&](int kc) {
+#pragma unroll
+			for (int c = 0; c < 8; ++c) ra[c] = arow ? ap[(int64_t)(kc + c) * ld] : 0.0;
+#pragma unroll
+			for (int c = 0; c < 2; ++c) rb[c] = *reinterpret_cast<const v2*>(bp + kc + 2 * c);
+		};
+		v4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+		fetch(0);
+		for (int kc = 0; kc < kend; kc += 32) {
+#pragma unroll
+			for (int c = 0; c < 4; ++c) *reinterpret_cast<v2*>(As + ar * LB_LDS + ak + 2 * c) = v2{ra[2 * c], ra[2 * c + 1]};
+#pragma unroll
+			for (int c = 0; c < 2; ++c) *reinterpret_cast<v2*>(Bs + br * LB_LDS + bk + 2 * c) = rb[c];
+			__syncthreads();
+			if (kc + 32 < kend) fetch(kc + 32);
+#pragma unroll
+			for (int kk = 0; kk < 8; ++kk) {
+				const double a = As[(16 * w + fr) * LB_LDS + 4 * kk + fk];
+				const double b0 = Bs[fr * LB_LDS + 4 * kk + fk], b1 = Bs[(16 + fr) * LB_LDS + 4 * kk + fk];
+				acc0 = Mfma<double>::mma(a, b0, acc0);
+				acc1 = Mfma<double>::mma(a, b1, acc1);
+			}
+			__syncthreads();
+		}
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			q0 = fma(acc0[i], acc0[i], q0);
+			q1 = fma(acc1[i], acc1[i], q1);
+		}
+	}
+	// (lanes fr, fr + 16, fr + 32, fr + 48 hold the four row groups of column fr: a symmetric tree, then the four waves in index order)
+	q0 += __shfl_xor(q0, 16); q0 += __shfl_xor(q0, 32);
+	q1 += __shfl_xor(q1, 16); q1 += __shfl_xor(q1, 32);
+	if (lane < 16) {
+		ssq[w][fr] = q0;
+		ssq[w][16 + fr] = q1;
+	}
+	__syncthreads();
+	if (tid < mt) var[tid] = p.kappa - (((ssq[0][tid] + ssq[1][tid]) + ssq[2][tid]) + ssq[3][tid]);
+}
+
+// one thread per test point, experts in expert order (the table of stpy_experts_combine in the header)
+__global__ __launch_bounds__(256)
+void experts_combine_kernel(int mode, int64_t E, int64_t M, const double* mu_e, const double* var_e, int64_t ldm, double kappa, double* mu, double* var)
+{
+	const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (t >= M) return;
+	const double vmin = kappa * 2.220446049250313e-16, logk = log(kappa), inv_e = 1.0 / (double)E;
+	double prec = 0.0, wm = 0.0, bsum = 0.0;
+	for (int64_t e = 0; e < E; ++e) {
+		const double v = fmin(fmax(var_e[e * ldm + t], vmin), kappa);
+		const double c = 1.0 / v;
+		const double beta = mode == 1 ? inv_e : (mode == 3 ? 0.5 * (logk - log(v)) : 1.0);
+		prec = fma(beta, c, prec);
+		wm = fma(beta * c, mu_e[e * ldm + t], wm);
+		bsum += beta;
+	}
+	if (mode == 2) prec += (1.0 - (double)E) / kappa;
+	if (mode == 3) prec += (1.0 - bsum) / kappa;
+	const double vout = 1.0 / prec;
+	var[t] = vout;
+	mu[t] = vout * wm;
+}
+
+}  // namespace stpy
+
+// ---- C ABI (include/stpy_hip.h); every refusal below comes before the first HIP call
+using namespace stpy;
+
+static bool experts_common_refused(const char* who, int kind, int dtype, int64_t N, int64_t ldx, int d, int64_t E, int64_t nmax, int* rc)
+{
+	*rc = 0;
+	if (dtype != STPY_F64) { set_error("%s: dtype %d: the local experts are float64 only (0)", who, dtype); *rc = -2; }
+	else if (kind < STPY_K_SE || kind > STPY_K_MATERN52) { set_error("%s: kernel kind %d is not one stationary term (SE, MATERN12/32/52)", who, kind); *rc = -1; }
+	else if (nmax < 0 || nmax > LB_MAX_N) { set_error("%s: nmax=%lld outside [0, %d] (stpy_experts_max_n)", who, (long long)nmax, LB_MAX_N); *rc = -4; }
+	else if (N < 0 || N > INT32_MAX || E < 0 || E > INT32_MAX) { set_error("%s: N=%lld E=%lld out of range", who, (long long)N, (long long)E); *rc = -9; }
+	else if (d < 1) { set_error("%s: bad dimension d=%d", who, d); *rc = -6; }
+	else if (ldx < d) { set_error("%s: leading dimension ldx=%lld (d=%d)", who, (long long)ldx, d); *rc = -5; }
+	return *rc != 0;
+}
+
+extern "C" {
+
+int64_t stpy_experts_max_n(void) { return LB_MAX_N; }
+
+int64_t stpy_experts_factor_bytes(int dtype, int64_t nmax, int64_t E)
+{
+	return dtype != STPY_F64 || nmax <= 0 || nmax > LB_MAX_N || E <= 0 ? 0 : E * experts_factor_slice(nmax) * (int64_t)sizeof(double);
+}
+
+int64_t stpy_experts_fit_workspace_bytes(int dtype, int64_t nmax, int d, int64_t E)
+{
+	(void)d;
+	return dtype != STPY_F64 || nmax <= 0 || nmax > LB_MAX_N || E <= 0 ? 0 : E * experts_fit_slice(nmax) * (int64_t)sizeof(double);
+}
+
+int stpy_experts_fit(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const void* ys,
+                     const int32_t* offsets, int64_t E, int64_t nmax, const void* inv_ls, const void* noise, double kappa, double weight,
+                     const int32_t* pidx, int np, void* factor, int64_t factor_bytes, void* alpha, void* value, void* grad, int64_t ldg,
+                     void* total, int32_t* info, void* work, int64_t work_bytes, void* stream)
+{
+	if (E == 0 || N == 0) return 0;          // empty problem: nothing to write
+	int rc;
+	if (experts_common_refused("stpy_experts_fit", kind, dtype, N, ldx, d, E, nmax, &rc)) return rc;
+	if (grad && (np < 1 || ldg < (int64_t)np + 1)) {
+		set_error("stpy_experts_fit: with a gradient np=%d must be positive and ldg=%lld at least np + 1", np, (long long)ldg);
+		return np < 1 ? -16 : -19;
+	}
+	if (!xs || !ys || !offsets || !inv_ls || !noise || !factor || !alpha || !value || !total || !info || !work || (grad && !pidx)) {
+		set_error("stpy_experts_fit: null pointer");
+		return -3;
+	}
+	if (!(kappa > 0.0) || !is_finite(kappa) || !is_finite(weight)) { set_error("stpy_experts_fit: kappa=%g must be positive and finite, weight=%g finite", kappa, weight); return -11; }
+	const int64_t need = stpy_experts_fit_workspace_bytes(dtype, nmax, d, E), fneed = stpy_experts_factor_bytes(dtype, nmax, E);
+	if (work_bytes < need) {
+		set_error("stpy_experts_fit: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", (long long)work_bytes, (long long)need);
+		return -20;
+	}
+	if (factor_bytes < fneed) {
+		set_error("stpy_experts_fit: factor buffer of %lld bytes, %lld needed (stpy_experts_factor_bytes)", (long long)factor_bytes, (long long)fneed);
+		return -22;
+	}
+	if ((((uintptr_t)xs | (uintptr_t)ys | (uintptr_t)alpha) & 7) || (((uintptr_t)work | (uintptr_t)factor) & 15)) {
+		set_error("stpy_experts_fit: work and factor must be 16-byte aligned, xs / ys / alpha 8-byte");
+		return -21;
+	}
+	ExpertsFitArgs p{(const double*)xs, N, ldx, d, cols, (const double*)ys, offsets, (int)nmax, (const double*)inv_ls, (const double*)noise, kappa, weight,
+	                 pidx, grad ? np : 0, (double*)factor, experts_factor_slice(nmax), (double*)alpha, (double*)value, (double*)grad, ldg, info,
+	                 (double*)work, experts_fit_slice(nmax), kind};
+	hipStream_t st = (hipStream_t)stream;
+	if (grad) hipLaunchKernelGGL(experts_fit_kernel<true>, dim3((unsigned)E), dim3(256), 0, st, p);
+	else hipLaunchKernelGGL(experts_fit_kernel<false>, dim3((unsigned)E), dim3(256), 0, st, p);
+	hipLaunchKernelGGL(experts_total_kernel, dim3(1), dim3(64), 0, st, (const double*)value, (const double*)grad, ldg, grad ? np : 0, E, (double*)total);
+	return check_launch("experts_fit");
+}
+
+int64_t stpy_experts_predict_workspace_bytes(int dtype, int64_t nmax, int d, int64_t E, int64_t M)
+{
+	(void)d;
+	if (dtype != STPY_F64 || nmax <= 0 || nmax > LB_MAX_N || E <= 0 || M <= 0) return 0;
+	return E * ((M + EX_TILE - 1) / EX_TILE) * experts_predict_slice(nmax) * (int64_t)sizeof(double);
+}
+
+int stpy_experts_predict(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const int32_t* offsets,
+                         int64_t E, int64_t nmax, const void* inv_ls, double kappa, const void* factor, int64_t factor_bytes,
+                         const void* alpha, const int32_t* info, const void* xt, int64_t M, int64_t ldt,
+                         void* mu_e, void* var_e, int64_t ldm, void* work, int64_t work_bytes, void* stream)
+{
+	if (E == 0 || N == 0 || M == 0) return 0;
+	int rc;
+	if (experts_common_refused("stpy_experts_predict", kind, dtype, N, ldx, d, E, nmax, &rc)) return rc;
+	const int64_t ntiles = M < 0 ? 0 : (M + EX_TILE - 1) / EX_TILE;
+	if (M < 0 || E * ntiles > INT32_MAX) { set_error("stpy_experts_predict: M=%lld out of range (E x tiles of 32 test points must stay below 2^31)", (long long)M); return -9; }
+	if (ldt < d || ldm < M) { set_error("stpy_experts_predict: leading dimensions ldt=%lld (d=%d) ldm=%lld (M=%lld)", (long long)ldt, d, (long long)ldm, (long long)M); return ldt < d ? -5 : -13; }
+	if (!xs || !offsets || !inv_ls || !factor || !alpha || !info || !xt || !mu_e || !var_e || !work) { set_error("stpy_experts_predict: null pointer"); return -3; }
+	if (!(kappa > 0.0) || !is_finite(kappa)) { set_error("stpy_experts_predict: kappa=%g must be positive and finite", kappa); return -11; }
+	const int64_t need = stpy_experts_predict_workspace_bytes(dtype, nmax, d, E, M), fneed = stpy_experts_factor_bytes(dtype, nmax, E);
+	if (work_bytes < need) {
+		set_error("stpy_experts_predict: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", (long long)work_bytes, (long long)need);
+		return -20;
+	}
+	if (factor_bytes < fneed) {
+		set_error("stpy_experts_predict: factor buffer of %lld bytes, %lld needed (stpy_experts_factor_bytes)", (long long)factor_bytes, (long long)fneed);
+		return -22;
+	}
+	if ((((uintptr_t)xs | (uintptr_t)xt | (uintptr_t)alpha | (uintptr_t)mu_e | (uintptr_t)var_e) & 7) || (((uintptr_t)work | (uintptr_t)factor) & 15)) {
+		set_error("stpy_experts_predict: work and factor must be 16-byte aligned, the other arrays 8-byte");
+		return -21;
+	}
+	ExpertsPredictArgs p{(const double*)xs, N, ldx, d, cols, offsets, (int)nmax, (const double*)inv_ls, kappa, (const double*)factor, experts_factor_slice(nmax),
+	                     (const double*)alpha, info, (const double*)xt, M, ldt, (double*)mu_e, (double*)var_e, ldm, (double*)work, experts_predict_slice(nmax),
+	                     (int)ntiles, kind};
+	hipLaunchKernelGGL(experts_predict_kernel, dim3((unsigned)(E * ntiles)), dim3(256), 0, (hipStream_t)stream, p);
+	return check_launch("experts_predict");
+}
+
+int stpy_experts_combine(int mode, int64_t E, int64_t M, const void* mu_e, const void* var_e, int64_t ldm, double kappa, void* mu, void* var, void* stream)
+{
+	if (E == 0 || M == 0) return 0;
+	if (mode < 0 || mode > 3) { set_error("stpy_experts_combine: mode %d (0 PoE, 1 gPoE, 2 BCM, 3 rBCM)", mode); return -10; }
+	if (E < 0 || M < 0 || M > (int64_t)INT32_MAX * 256) { set_error("stpy_experts_combine: E=%lld M=%lld out of range", (long long)E, (long long)M); return -9; }
+	if (ldm < M) { set_error("stpy_experts_combine: leading dimension ldm=%lld (M=%lld)", (long long)ldm, (long long)M); return -13; }
+	if (!mu_e || !var_e || !mu || !var) { set_error("stpy_experts_combine: null pointer"); return -3; }
+	if (!(kappa > 0.0) || !is_finite(kappa)) { set_error("stpy_experts_combine: kappa=%g must be positive and finite", kappa); return -11; }
+	if (((uintptr_t)mu_e | (uintptr_t)var_e | (uintptr_t)mu | (uintptr_t)var) & 7) { set_error("stpy_experts_combine: arrays must be 8-byte aligned"); return -21; }
+	hipLaunchKernelGGL(experts_combine_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mode, E, M, (const double*)mu_e,
+	                   (const double*)var_e, ldm, kappa, (double*)mu, (double*)var);
+	return check_launch("experts_combine");
+}
+
+}  // extern "C"

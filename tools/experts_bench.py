@@ -1,0 +1,160 @@
+"""
+Local experts: what a fit, an evidence gradient and a prediction cost (DESIGN.md "Local experts").
+
+  kernels     stpy_experts_fit with and without a gradient at n_e = 256, E = 1024, d = 8, per expert, beside stpy_lml_batch at n = 256,
+              batch = 1024, d = 8 per candidate -- from this build and, with --parent-lib, from another build of libstpy_hip.so (the parent
+              commit's), the three alternating inside one process; stpy_experts_predict + stpy_experts_combine at M = 4096
+  end to end  LocalExpertsGaussianProcess at N = 1 048 576, d = 8, expert_size = 256: fit_gp, one log_marginal with its gradient, mean_std of
+              4096 points; workspace and factor bytes at that size
+
+Kernel times are device events around `--reps` back-to-back launches after a warm-up, median and spread over `--rounds` rounds; end-to-end times
+are host clocks around calls that end in a read-back or a synchronise.  Prints one JSON line.
+
+usage: python tools/experts_bench.py [--reps 5] [--rounds 5] [--parent-lib PATH] [--quick]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from stpy_amd import _lib  # noqa: E402
+
+
+def _events(fn, reps):
+	a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+	a.record()
+	for _ in range(reps):
+		fn()
+	b.record()
+	b.synchronize()
+	return a.elapsed_time(b) / reps
+
+
+def _stats(v):
+	v = np.asarray(v)
+	return {"median_ms": float(np.median(v)), "min_ms": float(v.min()), "max_ms": float(v.max())}
+
+
+def _lml_batch_call(lib, x, y, inv_ls, noise, pidx, kappa=1.0):
+	"""a closure that launches stpy_lml_batch of the library handle ``lib`` (this build's or another's) on fixed buffers"""
+	lib.stpy_lml_batch_workspace_bytes.restype, lib.stpy_lml_batch_workspace_bytes.argtypes = _lib.SIGNATURES["stpy_lml_batch_workspace_bytes"]
+	lib.stpy_lml_batch.restype, lib.stpy_lml_batch.argtypes = _lib.SIGNATURES["stpy_lml_batch"]
+	n, d, B = x.shape[0], x.shape[1], inv_ls.shape[0]
+	value = torch.empty(B, dtype=torch.float64, device=x.device)
+	grad = torch.empty((B, 2), dtype=torch.float64, device=x.device)
+	info = torch.empty(B, dtype=torch.int32, device=x.device)
+	work = torch.empty(int(lib.stpy_lml_batch_workspace_bytes(0, n, d, B)), dtype=torch.uint8, device=x.device)
+	keep = (value, grad, info, work)
+
+	def call():
+		rc = lib.stpy_lml_batch(0, 0, _lib.ptr(x), n, d, d, None, _lib.ptr(y), B, _lib.ptr(inv_ls), d, _lib.ptr(noise), kappa, 1.0, _lib.ptr(pidx), 1,
+								_lib.ptr(value), _lib.ptr(grad), 2, _lib.ptr(info), _lib.ptr(work), work.numel(), _lib.stream_ptr())
+		assert rc == 0, rc
+	call.keep = keep
+	return call
+
+
+def main():
+	ap = argparse.ArgumentParser()
+	ap.add_argument("--reps", type=int, default=5)
+	ap.add_argument("--rounds", type=int, default=5)
+	ap.add_argument("--parent-lib", default=None)
+	ap.add_argument("--quick", action="store_true")
+	a = ap.parse_args()
+	if not torch.cuda.is_available():
+		print(json.dumps({"tool": "experts_bench", "error": "no GPU: nothing measured"}))
+		return 1
+	dev = _lib.device()
+	lib = _lib.load()
+	gen = torch.Generator(device="cpu").manual_seed(0)
+	n_e, E, d, M = 256, (64 if a.quick else 1024), 8, (256 if a.quick else 4096)
+	ls, s = 0.8, 0.1
+	out = {"tool": "experts_bench", "library": lib.stpy_version().decode(), "n_e": n_e, "E": E, "d": d, "M": M, "reps": a.reps, "rounds": a.rounds}
+
+	# ---- kernels: E different blocks under one candidate / E candidates on one block
+	xs = torch.rand((E * n_e, d), generator=gen, dtype=torch.float64).to(dev)
+	ys = (torch.sin(3 * xs[:, 0]) + 0.1 * torch.randn(E * n_e, generator=gen, dtype=torch.float64).to(dev)).contiguous()
+	offsets = torch.arange(0, (E + 1) * n_e, n_e, dtype=torch.int32, device=dev)
+	inv_ls = torch.full((d,), 1.0 / ls, dtype=torch.float64, device=dev)
+	noise = torch.tensor([s], dtype=torch.float64, device=dev)
+	pidx = torch.zeros(d, dtype=torch.int32, device=dev)
+	factor = _lib.experts_factor(n_e, E, xs)
+	alpha = torch.empty(E * n_e, dtype=torch.float64, device=dev)
+	work = _lib.experts_fit_workspace(n_e, d, E, xs)
+	fit_grad = lambda: _lib.experts_fit(0, xs, ys, offsets, n_e, inv_ls, noise, 1.0, 1.0, factor, alpha, pidx=pidx, n_params=1, work=work)
+	fit_plain = lambda: _lib.experts_fit(0, xs, ys, offsets, n_e, inv_ls, noise, 1.0, 1.0, factor, alpha, work=work)
+	inv_b = inv_ls.reshape(1, d).repeat(E, 1).contiguous()
+	noise_b = noise.repeat(E).contiguous()
+	runs = {"experts_fit_grad": fit_grad, "experts_fit": fit_plain, "lml_batch": _lml_batch_call(lib, xs[:n_e], ys[:n_e], inv_b, noise_b, pidx)}
+	if a.parent_lib:
+		runs["lml_batch_parent"] = _lml_batch_call(ctypes.CDLL(os.path.abspath(a.parent_lib)), xs[:n_e], ys[:n_e], inv_b, noise_b, pidx)
+	info = fit_plain()[3]
+	xt = torch.rand((M, d), generator=gen, dtype=torch.float64).to(dev)
+	mu_e = torch.empty((E, M), dtype=torch.float64, device=dev)
+	var_e = torch.empty((E, M), dtype=torch.float64, device=dev)
+	mu, var = torch.empty(M, dtype=torch.float64, device=dev), torch.empty(M, dtype=torch.float64, device=dev)
+	chunk = max(32, min(M, (1 << 20) // E))
+	pwork = _lib._work(lib.stpy_experts_predict_workspace_bytes(0, n_e, d, E, chunk), xs)
+
+	def predict_combine():
+		for c in range(0, M, chunk):
+			_lib.experts_predict(0, xs, offsets, n_e, inv_ls, 1.0, factor, alpha, info, xt[c:c + chunk], mu_e[:, c:c + chunk], var_e[:, c:c + chunk], work=pwork)
+		_lib.experts_combine(3, mu_e, var_e, 1.0, mu, var)
+	runs["predict_combine"] = predict_combine
+	times = {k: [] for k in runs}
+	for k, fn in runs.items():          # warm-up: code objects, allocations
+		fn()
+	torch.cuda.synchronize()
+	for _ in range(a.rounds):          # alternating, so that a drift of the box hits every variant alike
+		for k, fn in runs.items():
+			times[k].append(_events(fn, a.reps))
+	assert int(info.any().item()) == 0
+	out["kernels"] = {k: dict(_stats(v), per_expert_us=float(np.median(v)) * 1e3 / E) for k, v in times.items()}
+	out["predict_chunk"] = chunk
+	out["bytes_at_E"] = {"factor": factor.numel(), "fit_workspace": work.numel(), "predict_workspace": pwork.numel()}
+	del factor, alpha, work, pwork, mu_e, var_e, runs
+	torch.cuda.empty_cache()
+
+	# ---- end to end
+	import stpy_amd
+	N = (1 << 14) if a.quick else (1 << 20)
+	x = torch.rand((N, d), generator=gen, dtype=torch.float64)
+	y = (torch.sin(3 * x[:, :1]) * torch.cos(2 * x[:, 1:2]) + 0.1 * torch.randn((N, 1), generator=gen, dtype=torch.float64))
+	xd, yd, xtd = x.to(dev), y.to(dev), xt
+	gp = stpy_amd.LocalExpertsGaussianProcess(gamma=ls, s=s, d=d, expert_size=n_e)
+	e2e = {"fit_gp": [], "evidence_grad": [], "mean_std": []}
+	for r in range(1 + max(a.rounds, 1)):          # (round 0 warms up)
+		torch.cuda.synchronize()
+		t0 = time.perf_counter()
+		gp.fit_gp(xd, yd)
+		torch.cuda.synchronize()
+		t1 = time.perf_counter()
+		g = torch.tensor([ls], dtype=torch.float64, requires_grad=True)
+		f = gp.log_marginal(gp.kernel_object, {'0': {'gamma': g, 'kappa': 1.0, 'group': list(range(d))}}, 1.0)
+		f.backward()
+		torch.cuda.synchronize()
+		t2 = time.perf_counter()
+		m_, s_ = gp.mean_std(xtd)
+		torch.cuda.synchronize()
+		t3 = time.perf_counter()
+		if r > 0:
+			e2e["fit_gp"].append((t1 - t0) * 1e3)
+			e2e["evidence_grad"].append((t2 - t1) * 1e3)
+			e2e["mean_std"].append((t3 - t2) * 1e3)
+	Ebig = gp.experts_info["E"]
+	out["end_to_end"] = dict({k: _stats(v) for k, v in e2e.items()}, N=N, E=Ebig, M=M, evidence=float(f.detach()), dgamma=float(g.grad), predict_chunk=gp._chunks(M)[0][1],
+							 factor_bytes=gp.experts_info["factor_bytes"], fit_workspace_bytes=int(lib.stpy_experts_fit_workspace_bytes(0, n_e, d, Ebig)),
+							 predict_workspace_bytes=int(lib.stpy_experts_predict_workspace_bytes(0, n_e, d, Ebig, gp._chunks(M)[0][1])))
+	print(json.dumps(out))
+	return 0
+
+
+if __name__ == "__main__":
+	sys.exit(main())
