@@ -35,8 +35,11 @@ import operator
 import torch
 
 from .. import _lib
-from ..estimator import Estimator, Euclidean
+from ..estimator import Estimator
 from ..kernels import KernelFunction
+
+
+_GRAD_NAMES = ("gamma", "ard_gamma", "cov")          # what the dense evidence differentiates: lengthscales and the map of a full-covariance item
 
 
 class _LogMarginalFn(torch.autograd.Function):
@@ -46,7 +49,7 @@ class _LogMarginalFn(torch.autograd.Function):
 	def forward(ctx, gp, kernel, X, weight, *tensors):
 		val, state = gp._log_marginal_value(kernel, X, weight)
 		ctx.gp, ctx.kernel, ctx.X, ctx.weight, ctx.state = gp, kernel, X, weight, state
-		ctx.params = gp._grad_params(X)
+		ctx.params = gp._grad_params(X, _GRAD_NAMES)
 		return val.clone()
 
 	@staticmethod
@@ -865,22 +868,10 @@ class GaussianProcess(Estimator):
 		1/2 tr((w K^-1 - alpha alpha^T) dK/dtheta) evaluated on the device (stpy_potri,
 		stpy_lml_weight, stpy_gemm_nt).
 		"""
-		params = self._grad_params(X)
+		params = self._grad_params(X, _GRAD_NAMES)
 		if params:
 			return _LogMarginalFn.apply(self, kernel, X, weight, *[t for (_, _, t) in params])
 		return self._log_marginal_value(kernel, X, weight)[0]
-
-	def _grad_params(self, X):
-		"""(key, name, tensor) for every hyper-parameter tensor that asks for a gradient."""
-		out = []
-		for key in sorted(X.keys()) if X else []:
-			for name in ("gamma", "ard_gamma", "cov"):
-				v = X[key].get(name) if isinstance(X[key], dict) else None
-				if torch.is_tensor(v) and v.requires_grad:
-					out.append((key, name, v))
-		if torch.is_tensor(self.s) and self.s.requires_grad:
-			out.append(("likelihood", "sigma", self.s))
-		return out
 
 	def _ensure_device_data(self, caller):
 		"""Data handed over by ``load_data`` goes to the device at its first use."""
@@ -1105,15 +1096,7 @@ class GaussianProcess(Estimator):
 			if type in ("rots", "groups", "covariance"):
 				raise NotImplementedError("optimize_params(type='%s') is outside the stpy_amd hot path" % type)
 			raise AttributeError("This quick-optimization is not implemented.")          # gauss_procc.py:698
-		params = {}
-		for key, dict2 in self.kernel_object.params_dict.items():
-			if 'gamma' in dict2.keys():
-				params[key] = {'gamma': (init_func, Euclidean(1), bounds)}
-			elif 'ard_gamma' in dict2.keys():
-				params[key] = {'ard_gamma': (init_func, Euclidean(len(dict2['group'])), bounds)}
-		if type == "bandwidth+noise":
-			s0 = self.s
-			params['likelihood'] = {'sigma': ((lambda k: s0), Euclidean(1), None)}          # init_func_noise = lambda x: self.s
+		params = self._bandwidth_params(type, init_func, bounds)
 		return self.optimize_params_general(params=params, restarts=restarts, optimizer=optimizer, regularizer_func=regularizer_func,
 											maxiter=maxiter, mingradnorm=mingradnorm, verbose=verbose, scale=scale, weight=weight,
 											save=save, save_name=save_name, parallel=parallel, cores=cores)

@@ -79,9 +79,9 @@ import scipy.linalg
 import torch
 
 from .. import _lib
-from ..estimator import Estimator, Euclidean
+from ..estimator import Estimator
 from ..kernels import KernelFunction
-from .nystrom_fea import _stationary_term
+from .nystrom_fea import _OVERRIDE_KEYS, _check_term_overrides, _stationary_term
 
 _OUT_OF_SCOPE = {
 	"log_marginal": "the log-determinant of a matrix that is never formed needs stochastic Lanczos quadrature (a randomised estimate, not the exact evidence)",
@@ -228,38 +228,10 @@ class IterativeGaussianProcess(Estimator):
 		return rank, Gn, Gn.t().contiguous(), sumlog, trace
 
 	# ------------------------------------------------------------------ the stochastic evidence
-	_X_KEYS = ("gamma", "ard_gamma", "kappa", "group", "offset", "nu")
-
 	def _check_overrides(self, kernel, X):
 		"""Host refusals of log_marginal_estimate; returns (X, the one stationary term it resolves to)."""
-		X = {} if X is None else X
-		if kernel is not self.kernel_object:
-			_stationary_term(kernel)
-		for key, item in X.items():
-			if str(key) != "0" or not isinstance(item, dict):
-				raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: overrides for kernel item %r; the matrix-free operator has ONE item, '0'" % (key,))
-			for name, v in item.items():
-				if name not in self._X_KEYS:
-					raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: override %r is not a lengthscale of a single stationary term "
-											  "(supported: 'gamma' / 'ard_gamma'; the stored %s pass through unchanged)" % (name, ", ".join(repr(k) for k in self._X_KEYS[2:])))
-				if name not in ("gamma", "ard_gamma") and torch.is_tensor(v) and v.requires_grad:
-					raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: no gradient with respect to %r (lengthscales and the noise only)" % name)
-		items = kernel._chain(X if X else None)
-		if len(items) != 1 or len(items[0]['terms']) != 1:
-			raise NotImplementedError("IterativeGaussianProcess.log_marginal_estimate: the overrides resolve to %d items; ONE stationary term is supported" % len(items))
-		return X, items[0]['terms'][0]
-
-	def _grad_params(self, X):
-		"""(key, name, tensor) for every hyper-parameter tensor that asks for a gradient (the convention of GaussianProcess)."""
-		out = []
-		for key in sorted(X.keys()):
-			for name in ("gamma", "ard_gamma"):
-				v = X[key].get(name)
-				if torch.is_tensor(v) and v.requires_grad:
-					out.append((key, name, v))
-		if torch.is_tensor(self.s) and self.s.requires_grad:
-			out.append(("likelihood", "sigma", self.s))
-		return out
+		return _check_term_overrides("IterativeGaussianProcess.log_marginal_estimate", "the matrix-free operator", self.kernel_object, kernel, X,
+									 "'gamma' / 'ard_gamma'; the stored %s pass through unchanged" % ", ".join(repr(k) for k in _OVERRIDE_KEYS[2:]))
 
 	def _probe_draws(self, n, dtype, device, probes):
 		width = n + min(self.precond_rank, n)
@@ -292,7 +264,7 @@ class IterativeGaussianProcess(Estimator):
 		X, term = self._check_overrides(kernel, X)
 		if self.x is None or self.y is None:
 			raise AttributeError("IterativeGaussianProcess.log_marginal_estimate needs data: call fit_gp first")
-		params = self._grad_params(X)
+		params = self._grad_params(X, ("gamma", "ard_gamma"))
 		if params:
 			return _EstimateFn.apply(self, term, weight, probes, params, *[t for (_, _, t) in params])
 		return self._estimate(term, weight, probes, [])[0]
@@ -406,15 +378,7 @@ class IterativeGaussianProcess(Estimator):
 			raise NotImplementedError("IterativeGaussianProcess.optimize_params_estimate(type='%s'): 'bandwidth' and 'bandwidth+noise' only" % type)
 		if regularizer is not None:
 			raise NotImplementedError("IterativeGaussianProcess.optimize_params_estimate: no regularizer")
-		params = {}
-		for key, dict2 in self.kernel_object.params_dict.items():
-			if 'gamma' in dict2.keys():
-				params[key] = {'gamma': (init_func, Euclidean(1), bounds)}
-			elif 'ard_gamma' in dict2.keys():
-				params[key] = {'ard_gamma': (init_func, Euclidean(len(dict2['group'])), bounds)}
-		if type == "bandwidth+noise":
-			s0 = self.s
-			params['likelihood'] = {'sigma': ((lambda k: s0), Euclidean(1), None)}
+		params = self._bandwidth_params(type, init_func, bounds)
 		view = _EstimateView.__new__(_EstimateView)
 		view.__dict__ = self.__dict__                                       # the same state: what the driver writes lands on this object
 		return view.optimize_params_general(params=params, restarts=restarts, optimizer=optimizer, maxiter=maxiter, mingradnorm=mingradnorm,

@@ -26,16 +26,15 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..estimator import Estimator, Euclidean
+from ..estimator import Estimator
 from ..kernels import KernelFunction
-from .nystrom_fea import _stationary_term
+from .nystrom_fea import _check_term_overrides, _stationary_term
 
 EXPERT_CAP = 512                     # stpy_experts_max_n(): checked against the library at the first fit (the constructor stays on the host)
 COMBINE_MODES = {"poe": 0, "gpoe": 1, "bcm": 2, "rbcm": 3}
 # test points of one predict launch: E * chunk stays at or below this many (mu_e, var_e) elements; the launch's workspace is 8 * 32 * ceil(chunk / 32)
 # * E * (largest expert rounded up to 32) bytes -- 2 GiB at experts of 256 points, 4 GiB at 512
 PREDICT_BUDGET = 1 << 20
-_X_KEYS = ("gamma", "ard_gamma", "kappa", "group", "offset", "nu")
 
 
 def balanced_sizes(n, expert_size):
@@ -309,37 +308,10 @@ class LocalExpertsGaussianProcess(Estimator):
 	# ------------------------------------------------------------------ the factorised evidence
 	def _check_overrides(self, kernel, X):
 		"""Host refusals of log_marginal; returns (X, the one stationary term the overrides resolve to)."""
-		X = {} if X is None else X
-		if kernel is not self.kernel_object:
-			_stationary_term(kernel)
-		for key, item in X.items():
-			if str(key) != "0" or not isinstance(item, dict):
-				raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: overrides for kernel item %r; the experts' kernel has ONE item, '0'" % (key,))
-			for name, v in item.items():
-				if name not in _X_KEYS:
-					raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: override %r is not a lengthscale of a single stationary term "
-											  "(supported: 'gamma' / 'ard_gamma')" % (name,))
-				if name not in ("gamma", "ard_gamma") and torch.is_tensor(v) and v.requires_grad:
-					raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: no gradient with respect to %r (lengthscales and the noise only)" % name)
-		items = kernel._chain(X if X else None)
-		if len(items) != 1 or len(items[0]['terms']) != 1:
-			raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: the overrides resolve to %d items; ONE stationary term is supported" % len(items))
-		term = items[0]['terms'][0]
+		X, term = _check_term_overrides("LocalExpertsGaussianProcess.log_marginal", "the experts' kernel", self.kernel_object, kernel, X)
 		if term['premap'] is not None or term['pname'] is None or term['kind'] not in (_lib.K_SE, _lib.K_MATERN12, _lib.K_MATERN32, _lib.K_MATERN52):
 			raise NotImplementedError("LocalExpertsGaussianProcess.log_marginal: the %s kernel is not one stationary term" % kernel._term_name(term))
 		return X, term
-
-	def _grad_params(self, X):
-		"""(key, name, tensor) for every hyper-parameter tensor that asks for a gradient (the convention of GaussianProcess)."""
-		out = []
-		for key in sorted(X.keys()):
-			for name in ("gamma", "ard_gamma"):
-				v = X[key].get(name)
-				if torch.is_tensor(v) and v.requires_grad:
-					out.append((key, name, v))
-		if torch.is_tensor(self.s) and self.s.requires_grad:
-			out.append(("likelihood", "sigma", self.s))
-		return out
 
 	def _need_data(self, what):
 		if self._xs is None or self._xs.shape[0] == 0:
@@ -393,7 +365,7 @@ class LocalExpertsGaussianProcess(Estimator):
 		whose backward is the exact gradient, summed over the experts in expert order on the device.  The resident factor is left untouched."""
 		X, term = self._check_overrides(kernel, X)
 		self._need_data("log_marginal")
-		params = self._grad_params(X)
+		params = self._grad_params(X, ("gamma", "ard_gamma"))
 		if params:
 			return _ExpertsEvidenceFn.apply(self, term, weight, params, *[t for (_, _, t) in params])
 		return self._evidence(term, weight, [])[0]
@@ -437,14 +409,6 @@ class LocalExpertsGaussianProcess(Estimator):
 		if regularizer is not None:
 			raise NotImplementedError("LocalExpertsGaussianProcess.optimize_params: no regularizer")
 		self._need_data("optimize_params")
-		params = {}
-		for key, dict2 in self.kernel_object.params_dict.items():
-			if 'gamma' in dict2.keys():
-				params[key] = {'gamma': (init_func, Euclidean(1), bounds)}
-			elif 'ard_gamma' in dict2.keys():
-				params[key] = {'ard_gamma': (init_func, Euclidean(len(dict2['group'])), bounds)}
-		if type == "bandwidth+noise":
-			s0 = self.s
-			params['likelihood'] = {'sigma': ((lambda k: s0), Euclidean(1), None)}
+		params = self._bandwidth_params(type, init_func, bounds)
 		return self.optimize_params_general(params=params, restarts=restarts, optimizer=optimizer, maxiter=maxiter, mingradnorm=mingradnorm,
 											verbose=verbose, scale=scale, weight=weight, save=save, save_name=save_name, parallel=parallel, cores=cores)

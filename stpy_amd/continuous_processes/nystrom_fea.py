@@ -51,6 +51,29 @@ def _stationary_term(kernel_object):
 	return t
 
 
+_OVERRIDE_KEYS = ("gamma", "ard_gamma", "kappa", "group", "offset", "nu")
+
+
+def _check_term_overrides(who, owner, own_kernel, kernel, X, supported="'gamma' / 'ard_gamma'"):
+	"""Host refusals of an evidence that covers ONE stationary term and differentiates its lengthscales and the noise only: returns (X or {},
+	the one term ``kernel`` resolves to under the overrides ``X``).  ``who`` ("Class.method") and ``owner`` (what has the one item) word the messages."""
+	X = {} if X is None else X
+	if kernel is not own_kernel:
+		_stationary_term(kernel)
+	for key, item in X.items():
+		if str(key) != "0" or not isinstance(item, dict):
+			raise NotImplementedError("%s: overrides for kernel item %r; %s has ONE item, '0'" % (who, key, owner))
+		for name, v in item.items():
+			if name not in _OVERRIDE_KEYS:
+				raise NotImplementedError("%s: override %r is not a lengthscale of a single stationary term (supported: %s)" % (who, name, supported))
+			if name not in ("gamma", "ard_gamma") and torch.is_tensor(v) and v.requires_grad:
+				raise NotImplementedError("%s: no gradient with respect to %r (lengthscales and the noise only)" % (who, name))
+	items = kernel._chain(X if X else None)
+	if len(items) != 1 or len(items[0]['terms']) != 1:
+		raise NotImplementedError("%s: the overrides resolve to %d items; ONE stationary term is supported" % (who, len(items)))
+	return X, items[0]['terms'][0]
+
+
 def _pchol_device(kernel_object, xd, m, tol):
 	t = _stationary_term(kernel_object)
 	cols, inv_ls = kernel_object._term_operands(t, xd, xd.dtype, xd.device)

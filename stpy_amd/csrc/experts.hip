@@ -9,10 +9,10 @@
 //           fit to the predictions.
 //   work    fit: E slices of NPM^2 + 32 NPM doubles (A_e, then the inverse diagonal blocks); dead after the call.
 //           predict: one slice of 32 NPM doubles per (expert, test tile): the k* tile, TRANSPOSED (32 test points x NP_e).
-// The fit kernel is lml_batch_kernel with the expert's rows in place of the candidate's hyper-parameters, V in the factor buffer instead of the
-// workspace, alpha stored, and the K^-1 / H passes skipped without a gradient.  It is a kernel of its own so that stpy_lml_batch keeps its code.
+// The fit is lb_fit<GRAD, true> of lb_block.h, the body lml_batch_kernel calls too: here with the expert's rows in place of the candidate's
+// hyper-parameters, V in the factor buffer instead of the workspace, alpha stored, and the K^-1 / H passes left out without a gradient.
 //
-// Prediction, per (expert, tile of 32 test points): k* from direct differences with the evaluator of the fit (ex_r2 + lb_phi: the same bits on a
+// Prediction, per (expert, tile of 32 test points): k* from direct differences with the evaluator of the fit (lb_r2 + lb_phi: the same bits on a
 // training point), mu = k*^T alpha by one wave per test point, v = L^-1 k* = V^T k* on the fp64 MFMA 64 rows at a time -- lb_panel's loop with
 // the A tile fetched TRANSPOSED from V (V[k][i] is (L^-1)[i][k]; lanes run along i, so the global reads stay coalesced) -- and the column sums of
 // v o v straight from the accumulators: v is never stored.  The tile is 32 because that is the width of the panel product (two 16-column MFMA
@@ -21,7 +21,7 @@
 // Every sum has a fixed order and no workgroup reads what another wrote: an expert's outputs are bit-identical wherever it sits in whatever batch.
 // Compiled inside api.hip (which includes this file, as it includes pchol.hip and the kmv family; it also compiles on its own, as the resource
 // test does) and NOT beside lml_batch_kernel in reduce.hip: more kernels in that translation unit change its LDS layout and with it its instructions.
-// Barriers: as in lml_batch_kernel, every __syncthreads() is reached by the whole workgroup; the early exits test workgroup-uniform words.
+// Barriers: every __syncthreads() is reached by the whole workgroup; the early exits, here and in lb_fit, test workgroup-uniform words.
 #include "common.h"
 #include "lb_block.h"
 
@@ -50,198 +50,33 @@ inline int64_t experts_factor_slice(int64_t nmax) { return experts_npm(nmax) * e
 inline int64_t experts_fit_slice(int64_t nmax) { return experts_npm(nmax) * experts_npm(nmax) + 32 * experts_npm(nmax); }
 inline int64_t experts_predict_slice(int64_t nmax) { return EX_TILE * experts_npm(nmax); }
 
-// scaled squared distance of two rows from direct coordinate differences (the sum of lml_batch_kernel's lb_r2)
-__device__ __forceinline__ double ex_r2(const double* __restrict__ xi, const double* __restrict__ xj, const int32_t* __restrict__ cols,
-                                        const double* __restrict__ il, int d)
-{
-	double s = 0.0;
-	for (int k = 0; k < d; ++k) {
-		const int c = cols ? cols[k] : k;
-		const double u = (xi[c] - xj[c]) * il[k];
-		s = fma(u, u, s);
-	}
-	return s;
-}
-
+// The shell of lb_fit<GRAD, true> (lb_block.h) for expert blockIdx.x: the offsets check, then the expert's rows, its slice of the workspace (A_e, then
+// the inverse diagonal blocks) and of the factor buffer (V_e), its part of alpha.  Without a gradient the K^-1 / H passes are not compiled in.
 // (__launch_bounds__(256) and not (256, 2): the kernel needs about 200 VGPRs either way, two workgroups per CU, but under the tighter bound the
 // allocator parks one of the VGPRs that hold spilled SGPRs in scratch)
 template <bool GRAD>
 __global__ __launch_bounds__(256)
 void experts_fit_kernel(ExpertsFitArgs p)
 {
-	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
-	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
-	__shared__ double zs[LB_MAX_N], al[LB_MAX_N], red[4];
-	__shared__ int s_info;
-	const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int b = blockIdx.x, tid = threadIdx.x;
 	const int lo = p.offsets[b], hi = p.offsets[b + 1];
-	constexpr bool have_grad = GRAD;          // (without a gradient: no K^-1, no H, a kernel of its own)
-	double* grow = have_grad ? p.grad + (int64_t)b * p.ldg : nullptr;
-	if (tid == 0) {
-		s_info = 0;
-		if (have_grad)
-			for (int k = 0; k <= p.np; ++k) grow[k] = 0.0;
-	}
 	if (lo < 0 || hi < lo || hi > p.N || hi - lo > p.nmax) {          // (the same words for every thread) nothing of this expert is sized for: report it
 		const bool inside = lo >= 0 && hi >= lo && hi <= p.N;
 		if (inside)
 			for (int i = lo + tid; i < hi; i += 256) p.alpha[i] = 0.0;
 		if (tid == 0) {
+			if (GRAD)
+				for (int k = 0; k <= p.np; ++k) p.grad[(int64_t)b * p.ldg + k] = 0.0;
 			p.value[b] = __builtin_huge_val();
 			p.info[b] = inside ? -1 : -2;
 		}
 		return;
 	}
-	const int n = hi - lo, NP = (n + 31) & ~31, nblk = NP >> 5, ld = NP;
-	const double* x = p.xs + (int64_t)lo * p.ldx;
-	const double* y = p.ys + lo;
+	const int n = hi - lo, NP = (n + 31) & ~31;
 	double* A = p.work + (int64_t)b * p.wslice;
-	double* dinv = A + (int64_t)NP * NP;
-	double* V = p.factor + (int64_t)b * p.fslice;
-	const double* il = p.inv_ls;
-	const double sd = p.noise[0], s2 = sd * sd, kappa = p.kappa, wgt = p.weight;
-	const int ec = tid & 31, er = tid >> 5;              // entry of a 32 x 32 block in the elementwise passes: column, first of 4 rows (8 apart)
-
-	// ---- 1. lower blocks of K (whole diagonal blocks), identity border; the blocks of V just below its diagonal are stored as zero
-	for (int bi = 0; bi < nblk; ++bi)
-		for (int bj = 0; bj <= bi; ++bj)
-#pragma unroll
-			for (int q = 0; q < 4; ++q) {
-				const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
-				double v = i == j ? 1.0 : 0.0;
-				if (i < n && j < n) v = kappa * lb_phi(p.kind, ex_r2(x + (int64_t)i * p.ldx, x + (int64_t)j * p.ldx, p.cols, il, p.d)) + (i == j ? s2 : 0.0);
-				A[(int64_t)i * ld + j] = v;
-				if (bi == bj + 1) V[(int64_t)i * ld + j] = 0.0;
-			}
-
-	// ---- 2. Cholesky
-	for (int bk = 0; bk < nblk; ++bk) {
-		const int j0 = 32 * bk;
-		double* Ajj = A + (int64_t)j0 * ld + j0;
-		if (bk > 0) lb_panel<1>(Ajj, ld, A + (int64_t)j0 * ld, ld, A + (int64_t)j0 * ld, ld, NP - j0, j0, -1, As, Bs);
-		__syncthreads();
-		if (wave == 0) {
-			int bad;
-			[[clang::always_inline]] bad = lb_diag(A, V, ld, j0, dinv + bk * 1024, As);          // (two instances = two callers: the inliner would leave a call, and with it a stack)
-			if (bad != 0 && lane == 0) s_info = j0 + bad;
-		}
-		__syncthreads();
-		if (s_info != 0) {          // (the same word for every thread: the workgroup leaves as a whole)
-			for (int i = tid; i < n; i += 256) p.alpha[lo + i] = 0.0;
-			if (tid == 0) {
-				p.value[b] = __builtin_huge_val();
-				p.info[b] = s_info;
-			}
-			return;
-		}
-		if (j0 + 32 < NP) lb_panel<0>(Ajj + (int64_t)32 * ld, ld, Ajj + (int64_t)32 * ld, ld, dinv + bk * 1024, 32, NP - j0 - 32, 32, -1, As, Bs);
-	}
-	__syncthreads();
-	double logdiag = 0.0;
-	for (int i = tid; i < n; i += 256) logdiag += log(A[(int64_t)i * ld + i]);
-	logdiag = lb_block_sum(logdiag, red);
-
-	// ---- 3. V = L^-T: block column I from the finished columns left of it, V[0:i0, I] = -(V[0:i0, 0:i0] L[I, 0:i0]^T) dinv_I^T
-	for (int bk = 1; bk < nblk; ++bk) {
-		const int i0 = 32 * bk;
-		lb_panel<0>(V + i0, ld, V, ld, A + (int64_t)i0 * ld, ld, i0, i0, 0, As, Bs);
-		lb_panel<2>(V + i0, ld, V + i0, ld, dinv + bk * 1024, 32, i0, 32, -1, As, Bs);
-	}
-	__syncthreads();
-
-	// ---- 4. z = W y (z_i = sum_{k <= i} V[k][i] y_k), alpha = W^T z (alpha_j = sum_{k >= j} V[j][k] z_k)
-	for (int i = tid; i < NP; i += 256) {
-		const int kend = min(32 * (i / 32 + 1), n);
-		double z = 0.0;
-#pragma unroll 8
-		for (int k = 0; k < kend; ++k) z = fma(V[(int64_t)k * ld + i], y[k], z);
-		zs[i] = i < n ? z : 0.0;
-	}
-	__syncthreads();
-	for (int j = wave; j < n; j += 4) {
-		const double* vr = V + (int64_t)j * ld;
-		double s = 0.0;
-		for (int k = 32 * (j / 32) + lane; k < NP; k += 64) s = fma(vr[k], zs[k], s);
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-		if (lane == 0) al[j] = s;
-	}
-	__syncthreads();
-	double quad = 0.0, aa = 0.0;
-	for (int i = tid; i < n; i += 256) {
-		quad = fma(zs[i], zs[i], quad);
-		aa = fma(al[i], al[i], aa);
-		p.alpha[lo + i] = al[i];
-	}
-	quad = lb_block_sum(quad, red);
-	if (!have_grad) {
-		if (tid == 0) {
-			p.value[b] = 0.5 * quad + wgt * logdiag;
-			p.info[b] = 0;
-		}
-		return;
-	}
-	aa = lb_block_sum(aa, red);
-
-	// ---- K^-1 = V V^T over A's lower blocks (L is no longer needed), then H = (w K^-1 - alpha alpha^T) o kappa F below the diagonal
-	for (int bk = 0; bk < nblk; ++bk) {
-		const int j0 = 32 * bk;
-		lb_panel<0>(A + (int64_t)j0 * ld + j0, ld, V + (int64_t)j0 * ld, ld, V + (int64_t)j0 * ld, ld, NP - j0, NP, j0, As, Bs);
-	}
-	__syncthreads();
-	double tr = 0.0;
-	for (int bi = 0; bi < nblk; ++bi)
-		for (int bj = 0; bj <= bi; ++bj)
-#pragma unroll
-			for (int q = 0; q < 4; ++q) {
-				const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
-				double h = 0.0;
-				if (i < n && j <= i) {
-					const double kv = A[(int64_t)i * ld + j];
-					if (i == j) tr += kv;
-					else h = (wgt * kv - al[i] * al[j]) * kappa * lb_dfactor(p.kind, ex_r2(x + (int64_t)i * p.ldx, x + (int64_t)j * p.ldx, p.cols, il, p.d));
-				}
-				A[(int64_t)i * ld + j] = h;
-			}
-	tr = lb_block_sum(tr, red);          // (its barriers also order the H stores before the passes below: each entry is re-read by the thread that wrote it anyway)
-
-	// ---- lengthscale sums: 1/2 sum_ij H_ij u_m^2 / l_m = inv_ls_m sum_{i > j} H_ij u_m^2, four coordinates per pass over H
-	for (int m0 = 0; m0 < p.d; m0 += 4) {
-		double sm[4] = {0.0, 0.0, 0.0, 0.0};
-		for (int bi = 0; bi < nblk; ++bi)
-			for (int bj = 0; bj <= bi; ++bj)
-#pragma unroll
-				for (int q = 0; q < 4; ++q) {
-					const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
-					if (i < n && j < i) {
-						const double h = A[(int64_t)i * ld + j];
-						const double* xi = x + (int64_t)i * p.ldx;
-						const double* xj = x + (int64_t)j * p.ldx;
-#pragma unroll
-						for (int e = 0; e < 4; ++e)
-							if (m0 + e < p.d) {
-								const int c = p.cols ? p.cols[m0 + e] : m0 + e;
-								const double u = (xi[c] - xj[c]) * il[m0 + e];
-								sm[e] = fma(h, u * u, sm[e]);
-							}
-					}
-				}
-#pragma unroll
-		for (int e = 0; e < 4; ++e) sm[e] = lb_block_sum(sm[e], red);
-		if (tid == 0) {
-#pragma unroll
-			for (int e = 0; e < 4; ++e)
-				if (m0 + e < p.d) {
-					const int pi = p.pidx[m0 + e];
-					if (pi >= 0 && pi < p.np) grow[pi] += sm[e] * il[m0 + e];
-				}
-		}
-	}
-	if (tid == 0) {
-		p.value[b] = 0.5 * quad + wgt * logdiag;
-		grow[p.np] = sd * (wgt * tr - aa);
-		p.info[b] = 0;
-	}
+	lb_fit<GRAD, true>(LbFit{p.xs + (int64_t)lo * p.ldx, p.ldx, n, p.d, p.cols, p.ys + lo, p.inv_ls, p.noise[0], p.kappa, p.weight, p.pidx, p.np, p.kind,
+	                   A, p.factor + (int64_t)b * p.fslice, A + (int64_t)NP * NP, p.alpha + lo, p.value + b,
+	                   GRAD ? p.grad + (int64_t)b * p.ldg : nullptr, p.info + b});
 }
 
 // total[0] = sum_e value[e], total[1 + q] = sum_e grad[e*ldg + q] (q <= np; only with a gradient): one workgroup, thread q owns output q and adds
@@ -294,7 +129,7 @@ void experts_predict_kernel(ExpertsPredictArgs p)
 		const double* xk = x + (int64_t)k * p.ldx;
 		for (int t = 0; t < EX_TILE; ++t) {
 			double v = 0.0;
-			if (k < n && t < mt) v = p.kappa * lb_phi(p.kind, ex_r2(xk, p.xt + (t0 + t) * p.ldt, p.cols, il, p.d));
+			if (k < n && t < mt) v = p.kappa * lb_phi(p.kind, lb_r2(xk, p.xt + (t0 + t) * p.ldt, p.cols, il, p.d));
 			KT[(int64_t)t * ld + k] = v;
 		}
 	}

@@ -176,20 +176,11 @@ int lml_grad_cov_reduce(const T* x, int64_t n, int64_t ldx, int dg, const int32_
 // same data, ONE workgroup per candidate -- the restarts of a hyper-parameter search, each of which fills a small part of the chip
 // and costs ten launches and two host read-backs on the serial path.
 //
-// Per candidate, in its slice of the workspace (A, V: NP x NP row-major, NP = n rounded up to the block of 32, bordered by an identity;
-// dinv: the NP / 32 inverse diagonal blocks):
-//   1. A <- lower blocks of K = kappa phi(|(x_i - x_j)[cols] o inv_ls|) + s^2 I from direct coordinate differences;
-//   2. blocked left-looking Cholesky in place: panel -= (rows left of it) (its own rows left of it)^T on the fp64 MFMA, the 32 x 32
-//      diagonal block factored and inverted by one wave in registers (lane r holds row r; column values travel by v_readlane),
-//      the rows below it times the inverse block on the MFMA again;
-//   3. V <- L^-T (upper triangular, row-major = W^T for W = L^-1), block column by block column from V's finished part;
-//   4. z = W y, alpha = W^T z (LDS), then A <- K^-1 = V V^T (lower blocks), H = (w K^-1 - alpha alpha^T) o kappa F in place over it
-//      and the per-coordinate sums over i > j, four coordinates per pass over H.
-// Every sum has a fixed order (per-thread partial sums over a fixed set of entries, shuffle tree, four wave partials in index order)
-// and no candidate reads what another wrote: a candidate's outputs are bit-identical wherever it sits in whatever batch.
-// Barriers: every __syncthreads() below is reached by the whole workgroup -- the loops around them run over workgroup-uniform
-// ranges, the single-wave diagonal-block step has no barrier inside, and a failed pivot is published through LDS and read by all
-// threads behind a barrier, so the workgroup leaves as a whole.
+// The fit itself -- Gram fill, blocked Cholesky with the failed-pivot exit, V = L^-T, z and alpha, K^-1, H, the lengthscale sums -- is
+// lb_fit<true, false> of lb_block.h, the body this kernel shares with the local experts (experts.hip); its algorithm, its summation orders and
+// its barrier discipline are described there.  The kernel below is the shell: candidate b's inverse lengthscales, noise and gradient
+// row, and its slice of the workspace (A, V: NP x NP, NP = n rounded up to 32; dinv: the NP / 32 inverse diagonal blocks).  alpha is
+// not an output here.  No candidate reads what another wrote: a candidate's outputs are bit-identical wherever it sits in whatever batch.
 // ------------------------------------------------------------------------------------------
 struct LmlBatchArgs {
 	const double* x; int64_t ldx; int n, d; const int32_t* cols; const double* y;
@@ -206,167 +197,14 @@ inline int64_t lml_batch_slice_elems(int64_t n)
 	return 2 * np * np + 32 * np;
 }
 
-__device__ __forceinline__ double lb_r2(const LmlBatchArgs& p, const double* __restrict__ il, int i, int j)
-{
-	const double* xi = p.x + (int64_t)i * p.ldx;
-	const double* xj = p.x + (int64_t)j * p.ldx;
-	double s = 0.0;
-	for (int k = 0; k < p.d; ++k) {
-		const int c = p.cols ? p.cols[k] : k;
-		const double u = (xi[c] - xj[c]) * il[k];
-		s = fma(u, u, s);
-	}
-	return s;
-}
-
 __global__ __launch_bounds__(256, 2)
 void lml_batch_kernel(LmlBatchArgs p)
 {
-	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
-	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
-	__shared__ double zs[LB_MAX_N], al[LB_MAX_N], red[4];
-	__shared__ int s_info;
-	const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int n = p.n, NP = (n + 31) & ~31, nblk = NP >> 5, ld = NP;
+	const int b = blockIdx.x, NP = (p.n + 31) & ~31;
 	double* A = p.work + (int64_t)b * p.slice;
 	double* V = A + (int64_t)NP * NP;
-	double* dinv = V + (int64_t)NP * NP;
-	const double* il = p.inv_ls + (int64_t)b * p.ldi;
-	double* grow = p.grad + (int64_t)b * p.ldg;
-	const double sd = p.noise[b], s2 = sd * sd, kappa = p.kappa, wgt = p.weight;
-	const int ec = tid & 31, er = tid >> 5;              // entry of a 32 x 32 block in the elementwise passes: column, first of 4 rows (8 apart)
-	if (tid == 0) {
-		s_info = 0;
-		for (int k = 0; k <= p.np; ++k) grow[k] = 0.0;
-	}
-
-	// ---- 1. lower blocks of K (whole diagonal blocks), identity border; the blocks of V just below its diagonal are read as zero
-	for (int bi = 0; bi < nblk; ++bi)
-		for (int bj = 0; bj <= bi; ++bj)
-#pragma unroll
-			for (int q = 0; q < 4; ++q) {
-				const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
-				double v = i == j ? 1.0 : 0.0;
-				if (i < n && j < n) v = kappa * lb_phi(p.kind, lb_r2(p, il, i, j)) + (i == j ? s2 : 0.0);
-				A[(int64_t)i * ld + j] = v;
-				if (bi == bj + 1) V[(int64_t)i * ld + j] = 0.0;
-			}
-
-	// ---- 2. Cholesky
-	for (int bk = 0; bk < nblk; ++bk) {
-		const int j0 = 32 * bk;
-		double* Ajj = A + (int64_t)j0 * ld + j0;
-		if (bk > 0) lb_panel<1>(Ajj, ld, A + (int64_t)j0 * ld, ld, A + (int64_t)j0 * ld, ld, NP - j0, j0, -1, As, Bs);
-		__syncthreads();
-		if (wave == 0) {
-			const int bad = lb_diag(A, V, ld, j0, dinv + bk * 1024, As);
-			if (bad != 0 && lane == 0) s_info = j0 + bad;
-		}
-		__syncthreads();
-		if (s_info != 0) {          // (the same word for every thread: the workgroup leaves as a whole)
-			if (tid == 0) {
-				p.value[b] = __builtin_huge_val();
-				p.info[b] = s_info;
-			}
-			return;
-		}
-		if (j0 + 32 < NP) lb_panel<0>(Ajj + (int64_t)32 * ld, ld, Ajj + (int64_t)32 * ld, ld, dinv + bk * 1024, 32, NP - j0 - 32, 32, -1, As, Bs);
-	}
-	__syncthreads();
-	double logdiag = 0.0;
-	for (int i = tid; i < n; i += 256) logdiag += log(A[(int64_t)i * ld + i]);
-	logdiag = lb_block_sum(logdiag, red);
-
-	// ---- 3. V = L^-T: block column I from the finished columns left of it, V[0:i0, I] = -(V[0:i0, 0:i0] L[I, 0:i0]^T) dinv_I^T
-	for (int bk = 1; bk < nblk; ++bk) {
-		const int i0 = 32 * bk;
-		lb_panel<0>(V + i0, ld, V, ld, A + (int64_t)i0 * ld, ld, i0, i0, 0, As, Bs);
-		lb_panel<2>(V + i0, ld, V + i0, ld, dinv + bk * 1024, 32, i0, 32, -1, As, Bs);
-	}
-	__syncthreads();
-
-	// ---- 4. z = W y (z_i = sum_{k <= i} V[k][i] y_k), alpha = W^T z (alpha_j = sum_{k >= j} V[j][k] z_k)
-	for (int i = tid; i < NP; i += 256) {
-		const int kend = min(32 * (i / 32 + 1), n);
-		double z = 0.0;
-#pragma unroll 8
-		for (int k = 0; k < kend; ++k) z = fma(V[(int64_t)k * ld + i], p.y[k], z);
-		zs[i] = i < n ? z : 0.0;
-	}
-	__syncthreads();
-	for (int j = wave; j < n; j += 4) {
-		const double* vr = V + (int64_t)j * ld;
-		double s = 0.0;
-		for (int k = 32 * (j / 32) + lane; k < NP; k += 64) s = fma(vr[k], zs[k], s);
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-		if (lane == 0) al[j] = s;
-	}
-	__syncthreads();
-	double quad = 0.0, aa = 0.0;
-	for (int i = tid; i < n; i += 256) { quad = fma(zs[i], zs[i], quad); aa = fma(al[i], al[i], aa); }
-	quad = lb_block_sum(quad, red);
-	aa = lb_block_sum(aa, red);
-
-	// ---- K^-1 = V V^T over A's lower blocks (L is no longer needed), then H = (w K^-1 - alpha alpha^T) o kappa F below the diagonal
-	for (int bk = 0; bk < nblk; ++bk) {
-		const int j0 = 32 * bk;
-		lb_panel<0>(A + (int64_t)j0 * ld + j0, ld, V + (int64_t)j0 * ld, ld, V + (int64_t)j0 * ld, ld, NP - j0, NP, j0, As, Bs);
-	}
-	__syncthreads();
-	double tr = 0.0;
-	for (int bi = 0; bi < nblk; ++bi)
-		for (int bj = 0; bj <= bi; ++bj)
-#pragma unroll
-			for (int q = 0; q < 4; ++q) {
-				const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
-				double h = 0.0;
-				if (i < n && j <= i) {
-					const double kv = A[(int64_t)i * ld + j];
-					if (i == j) tr += kv;
-					else h = (wgt * kv - al[i] * al[j]) * kappa * lb_dfactor(p.kind, lb_r2(p, il, i, j));
-				}
-				A[(int64_t)i * ld + j] = h;
-			}
-	tr = lb_block_sum(tr, red);          // (its barriers also order the H stores before the passes below: each entry is re-read by the thread that wrote it anyway)
-
-	// ---- lengthscale sums: 1/2 sum_ij H_ij u_m^2 / l_m = inv_ls_m sum_{i > j} H_ij u_m^2, four coordinates per pass over H
-	for (int m0 = 0; m0 < p.d; m0 += 4) {
-		double sm[4] = {0.0, 0.0, 0.0, 0.0};
-		for (int bi = 0; bi < nblk; ++bi)
-			for (int bj = 0; bj <= bi; ++bj)
-#pragma unroll
-				for (int q = 0; q < 4; ++q) {
-					const int i = 32 * bi + er + 8 * q, j = 32 * bj + ec;
-					if (i < n && j < i) {
-						const double h = A[(int64_t)i * ld + j];
-						const double* xi = p.x + (int64_t)i * p.ldx;
-						const double* xj = p.x + (int64_t)j * p.ldx;
-#pragma unroll
-						for (int e = 0; e < 4; ++e)
-							if (m0 + e < p.d) {
-								const int c = p.cols ? p.cols[m0 + e] : m0 + e;
-								const double u = (xi[c] - xj[c]) * il[m0 + e];
-								sm[e] = fma(h, u * u, sm[e]);
-							}
-					}
-				}
-#pragma unroll
-		for (int e = 0; e < 4; ++e) sm[e] = lb_block_sum(sm[e], red);
-		if (tid == 0) {
-#pragma unroll
-			for (int e = 0; e < 4; ++e)
-				if (m0 + e < p.d) {
-					const int pi = p.pidx[m0 + e];
-					if (pi >= 0 && pi < p.np) grow[pi] += sm[e] * il[m0 + e];
-				}
-		}
-	}
-	if (tid == 0) {
-		p.value[b] = 0.5 * quad + wgt * logdiag;
-		grow[p.np] = sd * (wgt * tr - aa);
-		p.info[b] = 0;
-	}
+	lb_fit<true, false>(LbFit{p.x, p.ldx, p.n, p.d, p.cols, p.y, p.inv_ls + (int64_t)b * p.ldi, p.noise[b], p.kappa, p.weight, p.pidx, p.np, p.kind,
+	                   A, V, V + (int64_t)NP * NP, nullptr, p.value + b, p.grad + (int64_t)b * p.ldg, p.info + b});
 }
 
 int64_t lml_batch_workspace_bytes(int64_t n, int64_t batch)

@@ -67,6 +67,35 @@ class Estimator(ABC):
 		self.x = d[0]
 		self.y = d[1]
 
+	# ------------------------------------------------------------------ what the evidence and its search share between the estimators
+	def _grad_params(self, X, names):
+		"""(key, name, tensor) for every hyper-parameter tensor among ``names`` in the overrides ``X`` that asks for a gradient, items in key
+		order, then the noise std ``self.s`` as ("likelihood", "sigma", s) when it does.  ``names`` is what the caller's evidence can differentiate."""
+		out = []
+		for key in sorted(X.keys()) if X else []:
+			for name in names:
+				v = X[key].get(name) if isinstance(X[key], dict) else None
+				if torch.is_tensor(v) and v.requires_grad:
+					out.append((key, name, v))
+		if torch.is_tensor(self.s) and self.s.requires_grad:
+			out.append(("likelihood", "sigma", self.s))
+		return out
+
+	def _bandwidth_params(self, type, init_func, bounds):
+		"""The ``params`` dictionary of ``optimize_params_general`` for ``type`` in {"bandwidth", "bandwidth+noise"} (gauss_procc.py:640-702):
+		every kernel item's 'gamma' / 'ard_gamma' on a Euclidean factor, with "bandwidth+noise" also the noise std under the key 'likelihood',
+		started at its current value."""
+		params = {}
+		for key, dict2 in self.kernel_object.params_dict.items():
+			if 'gamma' in dict2.keys():
+				params[key] = {'gamma': (init_func, Euclidean(1), bounds)}
+			elif 'ard_gamma' in dict2.keys():
+				params[key] = {'ard_gamma': (init_func, Euclidean(len(dict2['group'])), bounds)}
+		if type == "bandwidth+noise":
+			s0 = self.s
+			params['likelihood'] = {'sigma': ((lambda k: s0), Euclidean(1), None)}          # init_func_noise = lambda x: self.s
+		return params
+
 	# ------------------------------------------------------------------ evidence of several candidates
 	def log_marginal_batch(self, kernel, Xs, weight, s=None):
 		"""Value and gradient of ``log_marginal`` for every override dictionary in ``Xs`` (and, with ``s``, its noise std): the

@@ -69,7 +69,7 @@ def test_lml_batch_argument_checks():
 
 # --------------------------------------------------------------------------------------------- 2. kernel resources
 def test_lml_batch_kernel_resources(tmp_path):
-	"""Every kernel of the batched evidence: no scratch, at most 64 KiB of LDS (two candidates share a CU)."""
+	"""Every kernel of the batched evidence: no scratch, at most 64 KiB of LDS and registers for two waves per SIMD (two candidates share a CU)."""
 	out = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment", "-c", os.path.join(CSRC, "reduce.hip"),
 						  "-o", str(tmp_path / "x.o"), "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, check=True).stderr
 	blocks = [b for b in re.split(r"remark: Function Name: ", out)[1:] if "lml_batch" in b.split()[0]]
@@ -78,6 +78,7 @@ def test_lml_batch_kernel_resources(tmp_path):
 		name = b.split()[0]
 		assert int(re.search(r"ScratchSize \[bytes/lane\]: (\d+)", b).group(1)) == 0, name
 		assert int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1)) <= 65536, name
+		assert int(re.search(r"Occupancy \[waves/SIMD\]: (\d+)", b).group(1)) >= 2, name
 
 
 # --------------------------------------------------------------------------------------------- 3. driver logic on an oracle-backed estimator

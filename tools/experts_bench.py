@@ -2,15 +2,17 @@
 Local experts: what a fit, an evidence gradient and a prediction cost (DESIGN.md "Local experts").
 
   kernels     stpy_experts_fit with and without a gradient at n_e = 256, E = 1024, d = 8, per expert, beside stpy_lml_batch at n = 256,
-              batch = 1024, d = 8 per candidate -- from this build and, with --parent-lib, from another build of libstpy_hip.so (the parent
-              commit's), the three alternating inside one process; stpy_experts_predict + stpy_experts_combine at M = 4096
+              batch = 1024, d = 8 per candidate -- from this build and, with --parent-lib (repeatable), from other builds of libstpy_hip.so
+              (the parent commit's), all alternating inside one process; "ratios" then holds, per entry point, this build over the first
+              parent and, with two parents, the per-round range of one parent over the other: the noise a ratio has to be read against;
+              stpy_experts_predict + stpy_experts_combine at M = 4096
   end to end  LocalExpertsGaussianProcess at N = 1 048 576, d = 8, expert_size = 256: fit_gp, one log_marginal with its gradient, mean_std of
               4096 points; workspace and factor bytes at that size
 
 Kernel times are device events around `--reps` back-to-back launches after a warm-up, median and spread over `--rounds` rounds; end-to-end times
 are host clocks around calls that end in a read-back or a synchronise.  Prints one JSON line.
 
-usage: python tools/experts_bench.py [--reps 5] [--rounds 5] [--parent-lib PATH] [--quick]
+usage: python tools/experts_bench.py [--reps 5] [--rounds 5] [--parent-lib PATH]... [--n 256] [--d 8] [--kernels-only] [--quick]
 """
 import argparse
 import ctypes
@@ -61,11 +63,33 @@ def _lml_batch_call(lib, x, y, inv_ls, noise, pidx, kappa=1.0):
 	return call
 
 
+def _experts_fit_call(lib, xs, ys, offsets, n_e, inv_ls, noise, pidx, factor, alpha, work, with_grad, kappa=1.0):
+	"""the same for stpy_experts_fit, with or without a gradient (one lengthscale slot); factor / alpha / work are shared between the variants"""
+	lib.stpy_experts_fit.restype, lib.stpy_experts_fit.argtypes = _lib.SIGNATURES["stpy_experts_fit"]
+	N, d, E = xs.shape[0], xs.shape[1], offsets.numel() - 1
+	value = torch.empty(E, dtype=torch.float64, device=xs.device)
+	grad = torch.empty((E, 2), dtype=torch.float64, device=xs.device) if with_grad else None
+	total = torch.empty(3, dtype=torch.float64, device=xs.device)
+	info = torch.empty(E, dtype=torch.int32, device=xs.device)
+
+	def call():
+		rc = lib.stpy_experts_fit(0, 0, _lib.ptr(xs), N, d, d, None, _lib.ptr(ys), _lib.ptr(offsets), E, n_e, _lib.ptr(inv_ls), _lib.ptr(noise), kappa, 1.0,
+								  _lib.ptr(pidx) if with_grad else None, 1 if with_grad else 0, _lib.ptr(factor), factor.numel(), _lib.ptr(alpha), _lib.ptr(value),
+								  _lib.ptr(grad), 2 if with_grad else 0, _lib.ptr(total), _lib.ptr(info), _lib.ptr(work), work.numel(), _lib.stream_ptr())
+		assert rc == 0, rc
+		return info
+	call.keep = (value, grad, total, info)
+	return call
+
+
 def main():
 	ap = argparse.ArgumentParser()
 	ap.add_argument("--reps", type=int, default=5)
 	ap.add_argument("--rounds", type=int, default=5)
-	ap.add_argument("--parent-lib", default=None)
+	ap.add_argument("--parent-lib", action="append", default=[])
+	ap.add_argument("--n", type=int, default=256, help="points per expert and per candidate")
+	ap.add_argument("--d", type=int, default=8)
+	ap.add_argument("--kernels-only", action="store_true")
 	ap.add_argument("--quick", action="store_true")
 	a = ap.parse_args()
 	if not torch.cuda.is_available():
@@ -74,7 +98,7 @@ def main():
 	dev = _lib.device()
 	lib = _lib.load()
 	gen = torch.Generator(device="cpu").manual_seed(0)
-	n_e, E, d, M = 256, (64 if a.quick else 1024), 8, (256 if a.quick else 4096)
+	n_e, E, d, M = a.n, (64 if a.quick else 1024), a.d, (256 if a.quick else 4096)
 	ls, s = 0.8, 0.1
 	out = {"tool": "experts_bench", "library": lib.stpy_version().decode(), "n_e": n_e, "E": E, "d": d, "M": M, "reps": a.reps, "rounds": a.rounds}
 
@@ -88,14 +112,16 @@ def main():
 	factor = _lib.experts_factor(n_e, E, xs)
 	alpha = torch.empty(E * n_e, dtype=torch.float64, device=dev)
 	work = _lib.experts_fit_workspace(n_e, d, E, xs)
-	fit_grad = lambda: _lib.experts_fit(0, xs, ys, offsets, n_e, inv_ls, noise, 1.0, 1.0, factor, alpha, pidx=pidx, n_params=1, work=work)
-	fit_plain = lambda: _lib.experts_fit(0, xs, ys, offsets, n_e, inv_ls, noise, 1.0, 1.0, factor, alpha, work=work)
 	inv_b = inv_ls.reshape(1, d).repeat(E, 1).contiguous()
 	noise_b = noise.repeat(E).contiguous()
-	runs = {"experts_fit_grad": fit_grad, "experts_fit": fit_plain, "lml_batch": _lml_batch_call(lib, xs[:n_e], ys[:n_e], inv_b, noise_b, pidx)}
-	if a.parent_lib:
-		runs["lml_batch_parent"] = _lml_batch_call(ctypes.CDLL(os.path.abspath(a.parent_lib)), xs[:n_e], ys[:n_e], inv_b, noise_b, pidx)
-	info = fit_plain()[3]
+	entries = ("experts_fit_grad", "experts_fit", "lml_batch")
+	suffixes = [""] + ["_parent" if i == 0 else "_parent%d" % (i + 1) for i in range(len(a.parent_lib))]
+	runs = {}
+	for sfx, handle in zip(suffixes, [lib] + [ctypes.CDLL(os.path.abspath(path)) for path in a.parent_lib]):
+		runs["experts_fit_grad" + sfx] = _experts_fit_call(handle, xs, ys, offsets, n_e, inv_ls, noise, pidx, factor, alpha, work, True)
+		runs["experts_fit" + sfx] = _experts_fit_call(handle, xs, ys, offsets, n_e, inv_ls, noise, pidx, factor, alpha, work, False)
+		runs["lml_batch" + sfx] = _lml_batch_call(handle, xs[:n_e], ys[:n_e], inv_b, noise_b, pidx)
+	info = runs["experts_fit"]()
 	xt = torch.rand((M, d), generator=gen, dtype=torch.float64).to(dev)
 	mu_e = torch.empty((E, M), dtype=torch.float64, device=dev)
 	var_e = torch.empty((E, M), dtype=torch.float64, device=dev)
@@ -112,15 +138,30 @@ def main():
 	for k, fn in runs.items():          # warm-up: code objects, allocations
 		fn()
 	torch.cuda.synchronize()
-	for _ in range(a.rounds):          # alternating, so that a drift of the box hits every variant alike
-		for k, fn in runs.items():
-			times[k].append(_events(fn, a.reps))
+	fits = [k for k in runs if k != "predict_combine"]
+	for r in range(a.rounds):          # alternating, so that a drift of the box hits every variant alike, and each round starting one variant later, so
+		for k in fits[r % len(fits):] + fits[:r % len(fits)]:          # that no variant always runs behind the same neighbour
+			times[k].append(_events(runs[k], a.reps))
+		runs["experts_fit"]()          # (the prediction reads this build's factor and alpha)
+		times["predict_combine"].append(_events(predict_combine, a.reps))
 	assert int(info.any().item()) == 0
 	out["kernels"] = {k: dict(_stats(v), per_expert_us=float(np.median(v)) * 1e3 / E) for k, v in times.items()}
+	if a.parent_lib:          # per round: this build over the first parent; with a second parent, parent over parent2 (what equal code measures)
+		ratio = lambda p, q: [float(x / y) for x, y in zip(times[p], times[q])]
+		out["ratios"] = {}
+		for k in entries:
+			r = ratio(k, k + "_parent")
+			out["ratios"][k] = {"new_over_parent_median": float(np.median(r)), "new_over_parent_min": min(r), "new_over_parent_max": max(r)}
+			if len(a.parent_lib) > 1:
+				pp = ratio(k + "_parent", k + "_parent2")
+				out["ratios"][k].update(parent_over_parent2_min=min(pp), parent_over_parent2_max=max(pp), parent_over_parent2_median=float(np.median(pp)))
 	out["predict_chunk"] = chunk
 	out["bytes_at_E"] = {"factor": factor.numel(), "fit_workspace": work.numel(), "predict_workspace": pwork.numel()}
 	del factor, alpha, work, pwork, mu_e, var_e, runs
 	torch.cuda.empty_cache()
+	if a.kernels_only:
+		print(json.dumps(out))
+		return 0
 
 	# ---- end to end
 	import stpy_amd
