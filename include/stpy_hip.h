@@ -31,7 +31,7 @@
  *         size): process-wide integers read at launch time, never written by the shipped host code -- tests/ use them to
  *         reach every shipped path at small sizes; they must not be changed while another thread is inside the library.
  *         Behaviour a caller may legitimately want per call is a `flags` argument instead (STPY_FLAG_*).  The timing
- *         experiments of tools/ (ablation bits, measured-and-dropped kernel variants, reserved-CU streams, in-kernel
+ *         experiments of tools/ (ablation bits, measured-and-dropped kernel variants, in-kernel
  *         stamps) are NOT in this library: they live in the lab build (make EXPERIMENTS=1 -> libstpy_hip_lab.so);
  *       * one sticky device error word per caller stream (part of the 64 bytes above), read by stpy_async_status;
  *   - exported symbols: exactly the functions declared in this header (the build hides everything else);

@@ -18,7 +18,8 @@ extern int g_trsm_right_looking, g_gemm_k128, g_rff_tile, g_trsv_flow, g_trsm_st
 // EXPERIMENT knobs: compile-time constants in the product library (the measured defaults); variables behind stpy_tune only in
 // the lab build (make EXPERIMENTS=1 -> libstpy_hip_lab.so, used by tools/).  The kernels and code paths that only a non-default
 // value reaches are compiled under #if STPY_LAB, so the product library does not carry them.  Where each default comes from is
-// documented at the place that reads it (gemm.hip, potrf.hip, solve.hip, rff.hip).
+// documented at the place that reads it (gemm.hip, potrf.hip, solve.hip, rff.hip).  Keys 2, 7, 10, 11, 12, 13, 24 and 31 belonged to potrf
+// experiments that were measured and removed ("Retired experiments"); they are not reused and stpy_tune_get answers -1 for them.
 #ifdef STPY_EXPERIMENTS
 #define STPY_LAB 1
 #define STPY_KNOB(key, name, dflt) extern int name;
@@ -27,10 +28,9 @@ extern int g_trsm_right_looking, g_gemm_k128, g_rff_tile, g_trsv_flow, g_trsm_st
 #define STPY_KNOB(key, name, dflt) constexpr int name = dflt;
 #endif
 #define STPY_KNOB_LIST(X) \
-	X(0, g_gemm_stagger, 40000) X(1, g_gemm_exp, 0) X(2, g_potf2_scalar, 0) X(3, g_trsm_pass_depth, 1024) X(4, g_trsm_wg_target, 2048) \
-	X(6, g_gemm_dtv, 1) X(7, g_potrf_diag_first_below, 0) X(10, g_potrf_beside_min, 0) X(11, g_potf2_sliver, 0) \
-	X(12, g_potrf_reserve_below, 0) X(13, g_potrf_reserve_above, 2048) X(14, g_potrf_nb256_upto, 2048) X(15, g_potrf_nb512_upto, 16384) \
-	X(18, g_potrf_strip, 0) X(19, g_rff_wgs, 0) X(20, g_gemm_tri_diag_last, 0) X(21, g_potrf_serial_below, 3200) X(22, g_trsv_fault_ticket, 0) X(23, g_potrf_nb1024_upto, 32768) X(24, g_potrf_first_nb, 0) X(25, g_potrf_nb2048_upto, 1 << 30) X(29, g_potf2_flow, 1) X(31, g_potrf_serial_band, 0) X(33, g_potrf_planes_min_tiles, 800)
+	X(0, g_gemm_stagger, 40000) X(1, g_gemm_exp, 0) X(3, g_trsm_pass_depth, 1024) X(4, g_trsm_wg_target, 2048) \
+	X(6, g_gemm_dtv, 1) X(14, g_potrf_nb256_upto, 2048) X(15, g_potrf_nb512_upto, 16384) \
+	X(18, g_potrf_strip, 0) X(19, g_rff_wgs, 0) X(20, g_gemm_tri_diag_last, 0) X(21, g_potrf_serial_below, 3200) X(22, g_trsv_fault_ticket, 0) X(23, g_potrf_nb1024_upto, 32768) X(25, g_potrf_nb2048_upto, 1 << 30) X(29, g_potf2_flow, 1) X(33, g_potrf_planes_min_tiles, 800)
 STPY_KNOB_LIST(STPY_KNOB)
 constexpr int g_gemm_dtv_min_k = 64;
 // panel width when the caller passes nb = 0: narrower panels shorten the latency-bound panel chain, which a
@@ -51,11 +51,7 @@ inline bool is_finite(double v) { return v >= -F64_MAX && v <= F64_MAX; }
 // ---- drive two streams never share a side stream or an event, and calls on ONE stream are ordered by that stream.
 struct LookAhead {
 	hipStream_t side = nullptr;
-	hipEvent_t col_ready = nullptr, panel_done = nullptr, trail_done = nullptr;
-	// "reserved" mode of potrf: update stream masked off one CU per XCD, diagonal-block stream masked onto those CUs
-	hipStream_t upd = nullptr, diag = nullptr;          // created on first use (potrf.hip: lookahead_reserved_streams)
-	bool reserved_tried = false;
-	hipEvent_t ev_diag = nullptr, ev_gemm = nullptr, ev_mode = nullptr;
+	hipEvent_t col_ready = nullptr, panel_done = nullptr;
 	// 64 bytes of device memory: ticket / published-count / error words of the one-launch vector solve (solve.hip)
 	void* trsv_sync = nullptr;
 };
@@ -135,7 +131,7 @@ inline int64_t potrf_workspace_bytes(int64_t n, int nb, int esize) { return 2 * 
 int gram_fill_f64(int kind, const double* as, const double* bs, const double* na, const double* nb, int dpad, int64_t n, int64_t q,
                   double kappa, double offset, double diag_add, int lower_only, int combine, double* out, int64_t ldo, hipStream_t st);      // recommended number of K passes for a product with few output tiles
 template <typename T>
-int potf2_trtri(T* A, int64_t lda, int nbk, T* W, T* P2, int64_t ldp2, int32_t* info, int block_row0, hipStream_t st, bool beside = false);
+int potf2_trtri(T* A, int64_t lda, int nbk, T* W, T* P2, int64_t ldp2, int32_t* info, int block_row0, hipStream_t st);
 template <typename T>
 int potrf(int64_t n, T* A, int64_t lda, T* winv, T* work, int nb, int32_t* info, hipStream_t st, int gflags = 0);
 template <typename T>

@@ -280,7 +280,7 @@ int gemm_nt_bf3p(int64_t m, int64_t n, int64_t k, const unsigned short* pl, int6
 	p.stl = 2;
 	{
 		const int64_t sm = (m + 1023) / 1024, sn = (n + 1023) / 1024;
-		if ((p.tri ? sm * (sm + 1) / 2 : sm * sn) < 128 && !(STPY_LAB && g_potrf_serial_band == -1)) p.stl = 1;          // fewer than 16 super-tiles per XCD: balance before locality (lab: knob 31 = -1 keeps the large ones, for the A/B)
+		if ((p.tri ? sm * (sm + 1) / 2 : sm * sn) < 128) p.stl = 1;          // fewer than 16 super-tiles per XCD: balance before locality
 	}
 	const int64_t se = (int64_t)256 << p.stl;
 	p.nst_m = (int)((m + se - 1) / se); p.nst_n = (int)((n + se - 1) / se);

@@ -14,7 +14,6 @@
 #include <atomic>
 #include <type_traits>
 #include <map>
-#include <vector>
 #include <mutex>
 
 #include "common.h"
@@ -23,150 +22,26 @@ namespace stpy {
 
 // default outer panel width: 1024 halves the read+write passes over the trailing matrix compared
 // with 512 (measured 2 % faster end to end at N = 65 536); the solves keep 512 (see solve.hip)
-// g_potf2_scalar = 0 (lab knob, key 2): 1 = the column-by-column VALU kernel (kept for A/B runs in the lab build)
 // stpy_tune key 18: the rows below a panel's diagonal block as one strip launch (solve.hip) instead of two products per 128 columns.
 // 0 (default): off.  1: every panel, on the look-ahead stream -- the strip kernel's 120-202 VGPRs wait for update workgroups to retire.
 // 2: only the first panel (nothing else on the chip: no measurable difference).  3: the look-ahead stream factors only the panel's
-// diagonal block and the strip runs on the update's stream after the trailing update (with key 12 the whole chain then sits on the
-// reserved CUs).  All slower than 0 (tools/potrf_sweep.py "18=0|1|3;12=0|16384", ms at N = 16 384 / 32 768 / 65 536: 34.5 / 190.7 / 1376
-// against 35.5 / 193 / 1381 (1), 35.8 / 197.5 / 1403 (3), 37.8 / 203 / 1407 (3 + reserved)): in the kernel trace the diagonal-block
-// kernel alone is 21 of the 35 ms at N = 16 384 (165 us average beside the update, 58 us alone) whatever surrounds it, and keeping
-// the update off eight CUs costs more than that kernel gains.
+// diagonal block and the strip runs on the caller's stream after the trailing update.  All slower than 0 (tools/potrf_sweep.py "18=0|1|3",
+// ms at N = 16 384 / 32 768 / 65 536: 34.5 / 190.7 / 1376 against 35.5 / 193 / 1381 (1), 35.8 / 197.5 / 1403 (3)): in the kernel trace
+// the diagonal-block kernel alone is 21 of the 35 ms at N = 16 384 (165 us average beside the update, 58 us alone) whatever surrounds it.
 // g_potrf_strip = 0 (lab knob, key 18)
 // g_potrf_serial_below = 3200:         stpy_tune key 21 (see potrf()): no look-ahead below this many remaining rows.  Round 3 had it off (the fully
                                        // serial order cost 42.4 ms at N = 16 384 against 35.2 overlapped).  Round 4: with the small trailing updates on the sliver
                                        // kernel (8-16 us instead of 36-40 per launch) the two event hand-overs of a look-ahead step (16 us each) cost more than the
                                        // overlap gains once fewer than ~3000 rows are left: potrf 0.50 -> 0.44 / 1.07 -> 0.93 / 2.34 -> 2.18 / 6.31 -> 6.12 /
                                        // 28.3 -> 28.2 ms at N = 1024 / 2048 / 4096 / 8192 / 16 384 (flat between 2100 and 4200, worse from 6400 on)
-// stpy_tune key 11 (0 = off, the default): blocks factored beside a trailing update take the 64-VGPR / four-wave form below.
-// Measured (tools/potrf_sweep.py, gpurun_out/potrf_sweep3.log): it is placed at once, as intended, but then RUNS 8x slower
-// beside the real update than alone (730-770 us against 94 us in the kernel trace) and loses to the eight-wave kernel that
-// waits for a slot (N = 16 384 potrf 41.0 ms against 36.7 ms).  Kept switchable for the next experiment, not used.
-// g_potf2_sliver = 0 (lab knob, key 11)
 constexpr int PT_THREADS = 512;
-constexpr int SLD = 132;     // LDS row stride in elements: 132 = 4 (mod 32) keeps the (row, k mod 4) lane map conflict-free
 
-#if STPY_LAB
+// ------------------------------------------------------------------------------------------
 // One workgroup: Cholesky of a (<=128)x(<=128) SPD block + inverse of its factor.
 //   A    : block in global memory (lower triangle read; L written back to the lower triangle)
 //   W    : 128x128 row-major, receives inverse(L) (zeros above the diagonal, identity padding)
 //   P2   : optional second copy of L (rows x 128 cols window of the panel workspace, zeros above the diagonal)
-// Thread map: 4 lanes per row (q = lane & 3 splits the k range), 128 rows -> 512 threads.
-template <typename T>
-__global__ __launch_bounds__(PT_THREADS)
-void potf2_trtri_kernel(T* __restrict__ A, int64_t lda, int nbk, T* __restrict__ W,
-                        T* __restrict__ P2, int64_t ldp2, int32_t* info, int block_row0)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	T* S = reinterpret_cast<T*>(smem_raw);          // [128][SLD]
-	T* dinv = S + IB * SLD;                         // [128]  1 / l_jj
-	T* ldiag = dinv + IB;                           // [128]  l_jj
-	const int tid = threadIdx.x;
-	const int row = tid >> 2, q = tid & 3;
-
-	// ---- load: lower triangle of the block, identity for the padding rows/cols
-	for (int idx = tid; idx < IB * IB; idx += PT_THREADS) {
-		const int i = idx >> 7, j = idx & 127;
-		T v = T(0);
-		if (i < nbk && j <= i) v = A[(int64_t)i * lda + j];
-		else if (i >= nbk && i == j) v = T(1);
-		S[i * SLD + j] = v;
-	}
-	__syncthreads();
-
-	// ---- potf2, left-looking by column: t_i = a_ij - sum_{k<j} l_ik l_jk for all rows i >= j.
-	// ---- S[j][j] keeps the pivot d_j (never overwritten: everybody reads it between the two
-	// ---- barriers); l_jj and 1/l_jj live in ldiag / dinv.
-	for (int j = 0; j < IB; ++j) {
-		T part = T(0);
-		if (row >= j) {
-			const T* si = S + row * SLD;
-			const T* sj = S + j * SLD;
-			// four independent partial sums: the LDS reads of a 16-deep step are all in flight together
-			T p1 = T(0), p2 = T(0), p3 = T(0);
-			int k = q;
-			for (; k + 12 < j; k += 16) {
-				part += si[k] * sj[k];
-				p1 += si[k + 4] * sj[k + 4];
-				p2 += si[k + 8] * sj[k + 8];
-				p3 += si[k + 12] * sj[k + 12];
-			}
-			for (; k < j; k += 4) part += si[k] * sj[k];
-			part += (p1 + p2) + p3;
-		}
-		part += __shfl_xor(part, 1);
-		part += __shfl_xor(part, 2);
-		if (row >= j && q == 0) S[row * SLD + j] -= part;
-		__syncthreads();
-		T d = S[j * SLD + j];
-		if (!(d > T(0)) || !(d < T(1e300))) {
-			if (tid == 0) atomicCAS(info, 0, block_row0 + j + 1);
-			d = T(1);
-		}
-		const T l = sqrt(d);
-		const T rl = T(1) / l;
-		if (q == 0) {
-			if (row > j) S[row * SLD + j] *= rl;
-			else if (row == j) { ldiag[j] = l; dinv[j] = rl; }
-		}
-		__syncthreads();
-	}
-
-	// ---- write L back (and the panel copy with explicit zeros above the diagonal)
-	for (int idx = tid; idx < IB * IB; idx += PT_THREADS) {
-		const int i = idx >> 7, j = idx & 127;
-		if (i < nbk && j < nbk) {
-			const T v = (j < i) ? S[i * SLD + j] : (j == i ? ldiag[i] : T(0));
-			if (j <= i) A[(int64_t)i * lda + j] = v;
-			if (P2) P2[(int64_t)i * ldp2 + j] = v;
-		}
-	}
-	__syncthreads();
-
-	// ---- trtri: column c of W = inverse(L) by forward substitution, W[k][c] kept at S[c][k]
-	// ---- (k >= c: the strict upper triangle + diagonal of S, which L no longer needs).
-	{
-		const int c = row;
-		if (q == 0) S[c * SLD + c] = dinv[c];
-		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-		__builtin_amdgcn_wave_barrier();
-		// the four lanes of a column and all 16 columns of a wave run the i loop together; a
-		// column simply idles until i passes its own index
-		const int cmin = (tid >> 6) * 16;          // first column handled by this wave
-		for (int i = cmin + 1; i < IB; ++i) {
-			T part = T(0);
-			if (i > c) {
-				const T* li = S + i * SLD;
-				const T* wc = S + c * SLD;
-				T p1 = T(0), p2 = T(0), p3 = T(0);
-				int k = c + q;
-				for (; k + 12 < i; k += 16) {
-					part += li[k] * wc[k];
-					p1 += li[k + 4] * wc[k + 4];
-					p2 += li[k + 8] * wc[k + 8];
-					p3 += li[k + 12] * wc[k + 12];
-				}
-				for (; k < i; k += 4) part += li[k] * wc[k];
-				part += (p1 + p2) + p3;
-			}
-			part += __shfl_xor(part, 1);
-			part += __shfl_xor(part, 2);
-			if (i > c && q == 0) S[c * SLD + i] = -part * dinv[i];
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-		}
-	}
-	__syncthreads();
-	for (int idx = tid; idx < IB * IB; idx += PT_THREADS) {
-		const int i = idx >> 7, c = idx & 127;
-		W[idx] = (c <= i) ? S[c * SLD + i] : T(0);
-	}
-}
-
-#endif  // STPY_LAB (scalar diagonal-block kernel)
-
-// ------------------------------------------------------------------------------------------
-// MFMA-blocked version of the same job (the default): the 128x128 block is processed in 16-wide
+// MFMA-blocked (stpy_tune key 29 = 0; the flow kernel further down is the default): the 128x128 block is processed in 16-wide
 // sub-blocks so that only the 16x16 diagonal sub-blocks see a serial pivot chain (one wave, rows in
 // registers, v_readlane broadcasts -- no LDS, no barriers inside it); the 16-wide panel below it,
 // the trailing update and the whole triangular inverse are 16x16x16 products on the MFMA.
@@ -902,241 +777,21 @@ void potf2_trtri_flow_kernel(TS* __restrict__ A, int64_t lda, int nbk, TS* W,
 #endif
 }
 
-#if STPY_LAB
-// ------------------------------------------------------------------------------------------
-// "Sliver" form of the same kernel for blocks factored WHILE a trailing update floods the chip (look-ahead panels):
-// 256 threads capped at 64 VGPRs and the same 83 KiB of LDS, i.e. it fits into what two update workgroups leave over on
-// a CU (512 - 2*224 VGPRs, 160 - 2*32 KiB) and is placed at once, where the eight-wave / 128-VGPR form above has to wait
-// for an update workgroup to exit -- 200-270 us per block in the kernel traces (tools/sliver_probe.hip: 79 us beside the
-// update = 79 us alone).  Same algorithm; what changes with four waves and a quarter of the registers:
-//   * the block is loaded in four batches of 16 values per thread;
-//   * sub-block rows / trailing pairs are dealt over 4 (3) waves instead of 8 (7);
-//   * the triangular inverse handles two block columns per wave, and finished blocks W_kj are re-read from the output
-//     array (L2-hot, written by the same wave) instead of being kept in registers.
-// ------------------------------------------------------------------------------------------
-constexpr int PS_THREADS = 256, PS_WAVES = 4;
 template <typename T>
-__global__ __launch_bounds__(PS_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8)))
-void potf2_trtri_sliver_kernel(T* __restrict__ A, int64_t lda, int nbk, T* W,
-                               T* __restrict__ P2, int64_t ldp2, int32_t* info, int block_row0)
-{
-	typedef Mfma<T> MM;
-	typedef typename MM::v4 v4;
-	extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-	T* S = reinterpret_cast<T*>(smem_raw);          // [TRI] packed lower triangle
-	T* WD = S + TRI;                                // [8][16][WLD]
-	T* SC = WD + NSB * SB * WLD;                    // [4 waves][16][WLD] scratch: C/D fragment -> B operand re-layout
-	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const int r16 = lane & 15, g = lane >> 4;
-	// beside two older, MFMA-saturating update waves per SIMD this kernel's serial pivot chain gets only leftover issue slots
-	// at equal priority (kernel trace: 730-770 us beside the update, 94 us alone): top priority for its whole life
-	__builtin_amdgcn_s_setprio(3);
-
-	{
-		// thread t owns column j = t & 127 and the rows i = (t >> 7) + 2 it: one base pointer and a uniform stride; eight loads in
-		// flight per batch (the eight-wave kernel keeps all 32 of a thread in registers, which 64 VGPRs cannot hold)
-		const int j = tid & 127, i0 = tid >> 7;
-		const T* src = A + (int64_t)i0 * lda + j;
-		const int64_t step = 2 * lda;
-		constexpr int NIT = IB * IB / PS_THREADS, BATCH = 8;
-#pragma unroll 1
-		for (int b0 = 0; b0 < NIT; b0 += BATCH) {
-			T v[BATCH];
-#pragma unroll
-			for (int it = 0; it < BATCH; ++it) {
-				const int i = i0 + 2 * (b0 + it);
-				v[it] = (j <= i && i < nbk) ? src[(int64_t)it * step] : ((i == j) ? T(1) : T(0));
-			}
-#pragma unroll
-			for (int it = 0; it < BATCH; ++it) {
-				const int i = i0 + 2 * (b0 + it);
-				if (j <= i) S[tri(i, j)] = v[it];
-			}
-			src += BATCH * step;
-		}
-	}
-	__syncthreads();
-
-	// ---- 16x16 diagonal sub-block (one wave): factor and inverse together, four lanes per row (see the kernel above)
-	auto diag_block = [&](int kb) {
-		const int o = kb * SB;
-		const int q = lane >> 4, i = lane & 15;
-		T a[4], w[4];
-#pragma unroll
-		for (int c = 0; c < 4; ++c) {
-			const int col = 4 * q + c;
-			a[c] = (col <= i) ? S[tri(o + i, o + col)] : T(0);
-			w[c] = (col == i) ? T(1) : T(0);
-		}
-		int first_bad = 0;
-		// (the group loop stays rolled: sixteen unrolled pivots hoist so many lane-permute addresses and constants that the
-		// kernel cannot stay within 64 VGPRs; inside a group the column index is a compile-time register index)
-#pragma unroll 1
-		for (int qj = 0; qj < 4; ++qj) {
-#pragma unroll
-			for (int cj = 0; cj < 4; ++cj) {
-				const int j = 4 * qj + cj;
-				T d = bcast(a[cj], 16 * qj + j);
-				const bool bad = !(d > T(0)) || !(d < T(1e300));
-				first_bad = (bad && first_bad == 0) ? j + 1 : first_bad;
-				d = bad ? T(1) : d;
-				T rl = (T)__builtin_amdgcn_rsq(d);
-				rl = rl * (T(1.5) - T(0.5) * d * rl * rl);
-				rl = rl * (T(1.5) - T(0.5) * d * rl * rl);
-				const T l = d * rl;
-				const T colv = (i == j) ? l : a[cj] * rl;
-				a[cj] = (q == qj && i >= j) ? colv : a[cj];
-				const T mi = __shfl(colv, 16 * qj + i, 64);
-#pragma unroll
-				for (int c = 0; c < 4; ++c) {
-					const int k = 4 * q + c;
-					const T lk = __shfl(colv, 16 * qj + 4 * q + c, 64);
-					const T wj = __shfl(w[c], 16 * q + j, 64);
-					const T na = a[c] - mi * lk;
-					a[c] = (k > j && i >= k) ? na : a[c];
-					const T ws = wj * rl;
-					const T nw = w[c] - mi * ws;
-					w[c] = (i == j) ? ws : ((i > j) ? nw : w[c]);
-				}
-			}
-		}
-		if (first_bad != 0 && lane == 0) atomicCAS(info, 0, block_row0 + o + first_bad);
-#pragma unroll
-		for (int c = 0; c < 4; ++c) {
-			const int col = 4 * q + c;
-			if (col <= i) S[tri(o + i, o + col)] = a[c];
-			WD[(kb * SB + i) * WLD + col] = (col <= i) ? w[c] : T(0);
-		}
-	};
-	auto trail_pair = [&](int kb, int bi, int bj) {
-		const int o = kb * SB;
-		const bool diag = bi == bj;
-		v4 acc;
-#pragma unroll
-		for (int q = 0; q < 4; ++q) {
-			const int rr = MM::crow(lane, q);
-			acc[q] = (!diag || r16 <= rr) ? S[tri(bi * SB + rr, bj * SB + r16)] : T(0);
-		}
-#pragma unroll
-		for (int s4 = 0; s4 < 4; ++s4)
-			acc = MM::mma(-S[tri(bi * SB + r16, o + 4 * s4 + g)], S[tri(bj * SB + r16, o + 4 * s4 + g)], acc);
-#pragma unroll
-		for (int q = 0; q < 4; ++q) {
-			const int rr = MM::crow(lane, q);
-			if (!diag || r16 <= rr) S[tri(bi * SB + rr, bj * SB + r16)] = acc[q];
-		}
-	};
-
-	// (one call site for the diagonal sub-block: the loop starts one step early, with only wave 0's first sub-block in it)
-#pragma unroll 1
-	for (int kb = -1; kb < NSB; ++kb) {
-		const int o = kb * SB;
-		if (kb >= 0) {
-			__syncthreads();
-			for (int bi = kb + 1 + wave; bi < NSB; bi += PS_WAVES) {           // panel below: X_bi = A_bi * WD^T
-				v4 acc = v4{0, 0, 0, 0};
-#pragma unroll
-				for (int s4 = 0; s4 < 4; ++s4)
-					acc = MM::mma(S[tri(bi * SB + r16, o + 4 * s4 + g)], WD[(kb * SB + r16) * WLD + 4 * s4 + g], acc);
-#pragma unroll
-				for (int q = 0; q < 4; ++q) S[tri(bi * SB + MM::crow(lane, q), o + r16)] = acc[q];
-			}
-			__syncthreads();
-		}
-		if (kb + 1 < NSB) {
-			if (kb >= 0) {
-				for (int bi = kb + 1 + wave; bi < NSB; bi += PS_WAVES) trail_pair(kb, bi, kb + 1);      // column kb+1 first
-				__syncthreads();
-			}
-			if (wave == 0) diag_block(kb + 1);
-			else if (kb >= 0) {
-				const int nrem = NSB - 2 - kb, npair = nrem * (nrem + 1) / 2;
-				for (int pidx = wave - 1; pidx < npair; pidx += PS_WAVES - 1) {
-					int a = 0, rem = pidx;
-					while (rem > a) { rem -= a + 1; ++a; }
-					trail_pair(kb, kb + 2 + a, kb + 2 + rem);
-				}
-			}
-		}
-	}
-	__syncthreads();
-
-	for (int idx = tid; idx < IB * IB; idx += PS_THREADS) {
-		const int i = idx >> 7, j = idx & 127;
-		const T v = (j <= i) ? S[tri(i, j)] : T(0);
-		if (i < nbk && j < nbk) {
-			if (j <= i) A[(int64_t)i * lda + j] = v;
-			if (P2) P2[(int64_t)i * ldp2 + j] = v;
-		}
-		const int bi = i >> 4, bj = j >> 4;
-		if (bj > bi) W[idx] = T(0);
-		else if (bj == bi) W[idx] = WD[(bi * SB + (i & 15)) * WLD + (j & 15)];
-	}
-
-	// ---- triangular inverse: wave w owns block columns w and w + 4; W_ij = -WD_i * sum_{k=j}^{i-1} L_ik W_kj, the finished
-	// ---- blocks of the column re-read from W (stores drained and ordered before the loads of the next step)
-	T* sc = SC + wave * SB * WLD;
-	for (int j = wave; j < NSB - 1; j += PS_WAVES) {
-		for (int i = j + 1; i < NSB; ++i) {
-			v4 t = v4{0, 0, 0, 0};
-			for (int k = j; k < i; ++k) {
-#pragma unroll
-				for (int s4 = 0; s4 < 4; ++s4) {
-					const T a = S[tri(i * SB + r16, k * SB + 4 * s4 + g)];
-					const T b = (k == j) ? WD[(j * SB + 4 * s4 + g) * WLD + r16] : W[(k * SB + 4 * s4 + g) * IB + j * SB + r16];
-					t = MM::mma(a, b, t);
-				}
-			}
-			v4 w = v4{0, 0, 0, 0};
-#pragma unroll
-			for (int q = 0; q < 4; ++q) sc[MM::crow(lane, q) * WLD + r16] = t[q];
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-			__builtin_amdgcn_wave_barrier();
-#pragma unroll
-			for (int s4 = 0; s4 < 4; ++s4) w = MM::mma(-WD[(i * SB + r16) * WLD + 4 * s4 + g], sc[(4 * s4 + g) * WLD + r16], w);
-#pragma unroll
-			for (int q = 0; q < 4; ++q) W[(i * SB + MM::crow(lane, q)) * IB + j * SB + r16] = w[q];
-			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-			__builtin_amdgcn_wave_barrier();          // (sc is rewritten by the next step only after every lane has read it)
-		}
-	}
-}
-
-#endif  // STPY_LAB (four-wave diagonal-block kernel)
-
-template <typename T>
-int potf2_trtri(T* A, int64_t lda, int nbk, T* W, T* P2, int64_t ldp2, int32_t* info, int block_row0, hipStream_t st, bool beside)
+int potf2_trtri(T* A, int64_t lda, int nbk, T* W, T* P2, int64_t ldp2, int32_t* info, int block_row0, hipStream_t st)
 {
 	const size_t lds_new = (size_t)(TRI + NSB * SB * WLD + (sizeof(T) == 4 ? 8 * SB * WLD : 0)) * sizeof(T);
 	const size_t lds_flow = (size_t)(TRI + NSB * SB * WLD) * sizeof(double);          // (the flow kernel computes in fp64 whatever the matrix type)
 	static std::atomic<bool> attr_set[2];          // (idempotent: two threads racing here both set the same attribute values)
 	const int which = sizeof(T) == 8 ? 0 : 1;
-#if STPY_LAB
-	const size_t lds_old = (size_t)(IB * SLD + 2 * IB) * sizeof(T);
-	const size_t lds_sliver = (size_t)(TRI + NSB * SB * WLD + PS_WAVES * SB * WLD) * sizeof(T);
-#endif
 	if (!attr_set[which].load(std::memory_order_acquire)) {
 		hipError_t e = hipFuncSetAttribute((const void*)potf2_trtri_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_new);
 		if (e == hipSuccess) e = hipFuncSetAttribute((const void*)potf2_trtri_flow_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_flow);
-#if STPY_LAB
-		if (e == hipSuccess) e = hipFuncSetAttribute((const void*)potf2_trtri_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_old);
-		if (e == hipSuccess) e = hipFuncSetAttribute((const void*)potf2_trtri_sliver_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sliver);
-#endif
 		if (e != hipSuccess) { set_error("potf2: hipFuncSetAttribute(%zu B LDS) failed: %s", lds_new, hipGetErrorString(e)); return -1000 - (int)e; }
 		attr_set[which].store(true, std::memory_order_release);
 	}
-#if STPY_LAB
-	if (g_potf2_scalar)
-		hipLaunchKernelGGL((potf2_trtri_kernel<T>), dim3(1), dim3(PT_THREADS), lds_old, st, A, lda, nbk, W, P2, ldp2, info, block_row0);
-	else if (beside && g_potf2_sliver)
-		hipLaunchKernelGGL((potf2_trtri_sliver_kernel<T>), dim3(1), dim3(PS_THREADS), lds_sliver, st, A, lda, nbk, W, P2, ldp2, info, block_row0);
-	else
-#endif
 	if (g_potf2_flow && (sizeof(T) == 8 || g_potf2_flow != 2)) hipLaunchKernelGGL((potf2_trtri_flow_kernel<T>), dim3(1), dim3(PT_THREADS), lds_flow, st, A, lda, nbk, W, P2, ldp2, info, block_row0);
 	else hipLaunchKernelGGL((potf2_trtri_mfma_kernel<T>), dim3(1), dim3(PT_THREADS), lds_new, st, A, lda, nbk, W, P2, ldp2, info, block_row0);
-	(void)beside;
 	return check_launch("potf2_trtri");
 }
 
@@ -1145,22 +800,6 @@ int potf2_trtri(T* A, int64_t lda, int nbk, T* W, T* P2, int64_t ldp2, int32_t* 
 // the small panel kernels are dispatched ahead of the queued trailing-update workgroups as CU slots free up.
 // Two host threads on two streams get two sets; calls on one stream are enqueued in program order and the events
 // of a set are only ever recorded / awaited by calls on that stream, so re-use across calls needs no further care.
-// g_potrf_diag_first_below = 0:        stpy_tune key 7 (8192 until round 4: with the flow-form diagonal-block kernel and the sliver updates starting the
-//                                       update only after the chain's first kernel no longer pays -- 6.13 -> 5.97 ms at N = 8192, 28.17 -> 28.08 at 16 384)
-// stpy_tune key 10: a look-ahead panel whose trailing update still has at least this many rows runs BESIDE that update and
-// takes the "sliver" GEMM for its panel products (gemm.hip: fits into what two update workgroups leave over on a CU, so it
-// is placed at once) instead of the tile kernels, which wait for an update workgroup to exit, or the 128 KiB one-volley
-// kernel, which needs a CU without any update workgroup.  tools/potrf_sweep.py, one process: with the threshold at 0 (every
-// look-ahead panel) potrf takes 10.2 / 36.7 / 194.4 / 1396 ms at N = 8192 / 16 384 / 32 768 / 65 536 against
-// 11.6 / 40.4 / 206.5 / 1411 ms without the beside mode.
-// g_potrf_beside_min = 0 (lab knob, key 10)
-// stpy_tune keys 12 / 13: trailing matrices with at most / at least this many rows are updated in reserved mode (see potrf());
-// 12 = 0 (the default) switches the mode off.  Measured, one process (tools/potrf_sweep.py, gpurun_out/potrf_sweep6.log): with the
-// mode on for every trailing matrix <= 24 576 rows potrf takes 10.5 / 38.7 / 208.0 / 1385 ms at N = 8192 / 16 384 / 32 768 /
-// 65 536 against 10.1 / 36.5 / 195.9 / 1371 ms without: the diagonal-block kernel does run at its stand-alone speed on its
-// reserved CU, but the update loses more (3 % of the CUs, 62 instead of 64 slots per XCD under a 64-tile super-tile map, and two
-// event hand-overs per 128-column block) than the chain gains.  Kept switchable; not used.
-// g_potrf_reserve_below = 0, g_potrf_reserve_above = 2048 (lab knobs, keys 12 / 13)
 // stpy_tune keys 14 / 15.  With the panel products in "beside" mode the chain of a wide panel is cheaper than it was, and wide
 // panels win (tools/potrf_sweep.py, gpurun_out/potrf_sweep8.log / 10.log, one process: N = 16 384 36.5 -> 34.4 ms, 32 768 196 -> 190 ms
 // against the former 16384 / 32768 thresholds; N = 65 536 unchanged within 0.2 %)
@@ -1184,8 +823,7 @@ int lookahead_acquire(hipStream_t caller, LookAhead** out)
 	(void)hipDeviceGetStreamPriorityRange(&lo, &hi);
 	if (hipStreamCreateWithPriority(&la->side, hipStreamNonBlocking, hi) != hipSuccess ||
 	    hipEventCreateWithFlags(&la->col_ready, hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&la->panel_done, hipEventDisableTiming) != hipSuccess ||
-	    hipEventCreateWithFlags(&la->trail_done, hipEventDisableTiming) != hipSuccess) {
+	    hipEventCreateWithFlags(&la->panel_done, hipEventDisableTiming) != hipSuccess) {
 		set_error("potrf: could not create the look-ahead stream/events");
 		delete la;
 		return -1002;
@@ -1195,50 +833,6 @@ int lookahead_acquire(hipStream_t caller, LookAhead** out)
 	*out = la;
 	return 0;
 }
-
-
-#if STPY_LAB
-// Created on first use only (the mode is off by default, stpy_tune key 12): masked streams alive at process exit have been
-// seen to crash the profiler's finalisation.
-static std::vector<LookAhead*> g_la_masked;          // objects that own CU-masked streams (guarded by g_la_mutex)
-static void destroy_masked_streams()                 // atexit: registered after the HIP runtime's own handlers, so it runs before them
-{
-	std::lock_guard<std::mutex> lock(g_la_mutex);
-	for (LookAhead* la : g_la_masked) {
-		if (la->upd) (void)hipStreamDestroy(la->upd);
-		if (la->diag) (void)hipStreamDestroy(la->diag);
-		la->upd = la->diag = nullptr;
-	}
-	g_la_masked.clear();
-}
-static void lookahead_reserved_streams(LookAhead* la)
-{
-	std::lock_guard<std::mutex> lock(g_la_mutex);
-	if (la->upd || la->reserved_tried) return;
-	la->reserved_tried = true;
-	static bool registered = false;
-	if (!registered) { registered = true; (void)atexit(destroy_masked_streams); }
-	// "reserved" mode (potrf, mid-size trailing matrices): the trailing update runs on a stream masked OFF one CU per XCD and
-	// the diagonal-block kernel on a stream masked ONTO those eight CUs.  Mask bits are dealt round-robin over the eight XCCs
-	// (tools/cumask_probe.hip: bits 0-7 = se0.cu0 of xcc0..7; an XCC whose bits are all clear gets ALL its CUs, so no XCC is
-	// ever left empty).  Failure to create them only switches the mode off.
-	{
-		unsigned m_upd[8], m_diag[8];
-		for (int w = 0; w < 8; ++w) { m_upd[w] = 0xffffffffu; m_diag[w] = 0u; }
-		m_upd[0] = 0xffffff00u;
-		m_diag[0] = 0x000000ffu;
-		if (hipExtStreamCreateWithCUMask(&la->upd, 8, m_upd) != hipSuccess || hipExtStreamCreateWithCUMask(&la->diag, 8, m_diag) != hipSuccess ||
-		    hipEventCreateWithFlags(&la->ev_diag, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&la->ev_gemm, hipEventDisableTiming) != hipSuccess ||
-		    hipEventCreateWithFlags(&la->ev_mode, hipEventDisableTiming) != hipSuccess) {
-			(void)hipGetLastError();
-			la->upd = la->diag = nullptr;
-		} else g_la_masked.push_back(la);
-	}
-}
-
-#else
-static void lookahead_reserved_streams(LookAhead*) {}          // (reserved-CU mode: lab build only; g_potrf_reserve_below is the constant 0 here)
-#endif
 
 template <typename T>
 static bool potrf_panel_can_strip(int64_t n, int64_t k, int64_t kb, const T* A, int64_t lda, const T* winv, int64_t ldp)
@@ -1251,13 +845,8 @@ static bool potrf_panel_can_strip(int64_t n, int64_t k, int64_t kb, const T* A, 
 // panel workspace P (n x nb, leading dimension nb, rows indexed globally).
 template <typename T>
 static int factor_panel(int64_t n, int64_t k, int64_t kb, T* A, int64_t lda, T* winv, T* P, int64_t ldp, int32_t* info, hipStream_t st,
-                        int gflags, hipEvent_t first_diag = nullptr, hipStream_t diag_st = nullptr, hipEvent_t ev_diag = nullptr, hipEvent_t ev_gemm = nullptr,
-                        int strip_mode = -1)          // -1: by stpy_tune key 18; 0: per-block products over all rows; 1: strip launch on `st`; 2: rows below left to the caller
+                        int gflags, int strip_mode = -1)          // -1: by stpy_tune key 18; 0: per-block products over all rows; 1: strip launch on `st`; 2: rows below left to the caller
 {
-	// diag_st != nullptr ("reserved" mode): the 128 x 128 diagonal-block kernel runs on its own stream, which is masked onto
-	// CUs the trailing update cannot use, with an event hand-over in each direction; the panel GEMMs stay on `st`.
-	const bool split = diag_st != nullptr && diag_st != st;
-#define FP_EV(x) do { if ((x) != hipSuccess) { set_error("potrf: event hand-over between the panel streams failed"); return -1003; } } while (0)
 	int rc;
 	// Rows below the panel's diagonal block: one strip launch after that block is factored (solve.hip: trsm_strip_kernel)
 	// instead of two products per 128 columns over all of them -- the chain of small kernels then only spans kb rows.
@@ -1274,15 +863,11 @@ static int factor_panel(int64_t n, int64_t k, int64_t kb, T* A, int64_t lda, T* 
 			rc = gemm_nt<T>(rows_end - c, cb, jj, P + c * ldp, ldp, P + c * ldp, ldp, A + c * lda + c, lda, (T*)nullptr, 0, 1, 0, st, nullptr, nullptr, nullptr, 1, nullptr, gflags);
 			if (rc) return rc;
 		}
-		hipStream_t ds = split ? diag_st : st;
-		if (split) { FP_EV(hipEventRecord(ev_gemm, st)); FP_EV(hipStreamWaitEvent(ds, ev_gemm, 0)); }
 		{
-			ProfScope ps(TAG_POTF2, (double)cb * cb * cb / 3.0, ds);
-			rc = potf2_trtri<T>(A + c * lda + c, lda, (int)cb, winv + (c / IB) * IB * IB, P + c * ldp + jj, ldp, info, (int)c, ds, !split && (gflags & GEMM_BESIDE) != 0);
+			ProfScope ps(TAG_POTF2, (double)cb * cb * cb / 3.0, st);
+			rc = potf2_trtri<T>(A + c * lda + c, lda, (int)cb, winv + (c / IB) * IB * IB, P + c * ldp + jj, ldp, info, (int)c, st);
 		}
 		if (rc) return rc;
-		if (c == k && first_diag && hipEventRecord(first_diag, ds) != hipSuccess) { set_error("potrf: event record failed"); return -1003; }
-		if (split) { FP_EV(hipEventRecord(ev_diag, ds)); FP_EV(hipStreamWaitEvent(st, ev_diag, 0)); }
 		if (c + cb < rows_end) {   // A[c+cb:n, c:c+cb] <- A[..] inverse(L_cc)^T, in place + copy into the panel
 			ProfScope ps(TAG_PANEL_GEMM, (double)(rows_end - c - cb) * (double)cb * (double)cb, st);   // triangular operand: half of 2mnk
 			rc = gemm_nt<T>(rows_end - c - cb, cb, cb, A + (c + cb) * lda + c, lda, winv + (c / IB) * IB * IB, IB,
@@ -1296,7 +881,6 @@ static int factor_panel(int64_t n, int64_t k, int64_t kb, T* A, int64_t lda, T* 
 		rc = trsm_strip<T>(mb, A + k * lda + k, lda, winv + (k / IB) * IB * IB, A + (k + kb) * lda + k, lda, P + (k + kb) * ldp, ldp, kb, st);
 		if (rc) return rc;
 	}
-#undef FP_EV
 	return 0;
 }
 
@@ -1308,7 +892,8 @@ static int factor_panel(int64_t n, int64_t k, int64_t kb, T* A, int64_t lda, T* 
 //                 update the rest of the trailing matrix A[r+nb:n, r+nb:n] -= Pk Pk^T (lower tiles)
 //   side stream : wait col_ready; factor panel k+1 into the OTHER workspace -> event panel_done
 //   main stream : wait panel_done before using panel k+1.
-// The two regions written concurrently are disjoint (columns [r, r+nb) vs columns >= r+nb) and the
+// Serial tail (stpy_tune key 21): with few rows left both updates and then panel k+1 run on the main stream, no events.
+// Everything is enqueued on `st` or on the side stream.  The two regions written concurrently are disjoint (columns [r, r+nb) vs columns >= r+nb) and the
 // trailing update reads only Pk, which the side stream never touches.
 template <typename T>
 int potrf(int64_t n, T* A, int64_t lda, T* winv, T* work, int nb, int32_t* info, hipStream_t st, int gflags)
@@ -1332,22 +917,9 @@ int potrf(int64_t n, T* A, int64_t lda, T* winv, T* work, int nb, int32_t* info,
 	auto width = [&](int64_t left) { const int64_t w = adaptive ? potrf_auto_nb(left) : nb; return left < w ? left : w; };
 
 	int64_t wk = width(n);                                          // width of the current panel
-	// (stpy_tune key 24: the FIRST panel has nothing to hide behind -- its n x wk left-looking products and wk / 128 diagonal blocks
-	// run alone on the chip -- so it may be narrower than the panels that follow)
-	if (adaptive && g_potrf_first_nb > 0 && g_potrf_first_nb % IB == 0 && g_potrf_first_nb < wk) wk = g_potrf_first_nb;
 	rc = factor_panel<T>(n, 0, wk, A, lda, winv, Pbuf[0], ldp, info, st, gflags);
 	if (rc) return rc;
 	int cur = 0;
-	// U: the stream the trailing updates run on -- the caller's, or (reserved mode) the one masked off one CU per XCD.  A
-	// change of mode orders the two streams through ev_mode; the caller's stream waits for the last update at the end.
-	hipStream_t U = st;
-	auto switch_to = [&](hipStream_t nu) -> int {
-		if (nu == U) return 0;
-		HIPCHK(hipEventRecord(la->ev_mode, U));
-		HIPCHK(hipStreamWaitEvent(nu, la->ev_mode, 0));
-		U = nu;
-		return 0;
-	};
 	// trailing update C[r0:n, r0:r0+cols] -= Pk[r0:n] Pk[r0:r0+cols]^T  (lower: cols = n - r0, lower tiles only), from the planes when `pre`
 	auto update = [&](T* Pk, bool pre, int64_t r0, int64_t cols, int64_t kk, int lower) -> int {
 		if constexpr (sizeof(T) == 4) {
@@ -1357,104 +929,81 @@ int potrf(int64_t n, T* A, int64_t lda, T* winv, T* work, int nb, int32_t* info,
 			const int64_t t = (n - r0) / 128, tiles = lower ? t * (t + 1) / 2 : t * (cols / 128);
 			const int64_t floor_t = g_gemm_sliver_tiles > 0 ? g_potrf_planes_min_tiles : 0;          // (slivers switched off: the planes from 128 / 64 tiles on)
 			if (pre && tiles >= (lower ? 128 : 64) && tiles > (lower ? floor_t : floor_t / 2))
-				return gemm_nt_bf3p(n - r0, cols, kk, planes, ldp, pstride, r0, r0, (float*)A + r0 * lda + r0, lda, lower, U);
+				return gemm_nt_bf3p(n - r0, cols, kk, planes, ldp, pstride, r0, r0, (float*)A + r0 * lda + r0, lda, lower, st);
 		}
-		return gemm_nt<T>(n - r0, cols, kk, Pk + r0 * ldp, ldp, Pk + r0 * ldp, ldp, A + r0 * lda + r0, lda, (T*)nullptr, 0, 1, lower, U);
+		return gemm_nt<T>(n - r0, cols, kk, Pk + r0 * ldp, ldp, Pk + r0 * ldp, ldp, A + r0 * lda + r0, lda, (T*)nullptr, 0, 1, lower, st);
 	};
 	for (int64_t k = 0; k + wk < n;) {
 		const int64_t r = k + wk;                                   // first row/column of the trailing matrix
 		const int64_t nkb = width(n - r);                           // width of the next panel
 		T* Pk = Pbuf[cur];
-		// Reserved mode: beside the real update the diagonal-block kernel is PLACED quickly but RUNS four to five times
-		// slower (in-kernel stamps, tools/potf2_stamps.py: 245-300 us against 58 us alone, every phase of it stretched alike),
-		// and it is the longest link of a chain that mid-size trailing matrices cannot hide.  With the update kept off one CU
-		// per XCD (3 % of the chip) that kernel runs alone on a reserved CU at its stand-alone speed.
-		const bool want_reserve = (n - r) <= g_potrf_reserve_below && (n - r) >= g_potrf_reserve_above && !(gflags & GEMM_BESIDE);
-		if (want_reserve && !la->upd) lookahead_reserved_streams(la);
-		const bool reserve = want_reserve && la->upd && (n - r) <= g_potrf_reserve_below && (n - r) >= g_potrf_reserve_above && !(gflags & GEMM_BESIDE);
-		rc = switch_to(reserve ? la->upd : st);
-		if (rc) return rc;
 		bool pre = false;
 		if constexpr (sizeof(T) == 4) {
 			pre = g_potrf_presplit && (n - r) % 128 == 0 && (n - r) >= 2048 && ((n - r) / 128) * ((n - r) / 128 + 1) / 2 > (g_gemm_sliver_tiles > 0 ? g_potrf_planes_min_tiles : 0) && wk % 32 == 0 && wk >= 64 && nkb % 128 == 0 && lda < (1 << 24) &&
 			      (((uintptr_t)Pk | (uintptr_t)planes) & 15) == 0 && n * ldp * 2 < ((int64_t)1 << 32);
 			if (pre) {
-				rc = bf3_split((const float*)Pk + r * ldp, ldp, n - r, wk, planes, ldp, pstride, r, U);
+				rc = bf3_split((const float*)Pk + r * ldp, ldp, n - r, wk, planes, ldp, pstride, r, st);
 				if (rc) return rc;
 			}
 		}
 		{   // next panel's block column (all rows below r)
-			ProfScope ps(TAG_SYRK, 2.0 * (double)(n - r) * (double)nkb * (double)wk - (double)nkb * (double)nkb * (double)wk, U);
+			ProfScope ps(TAG_SYRK, 2.0 * (double)(n - r) * (double)nkb * (double)wk - (double)nkb * (double)nkb * (double)wk, st);
 			rc = update(Pk, pre, r, nkb, wk, 0);
 			if (rc) return rc;
 		}
 		// key 18 = 3: the look-ahead stream factors only the panel's nkb x nkb diagonal block (the latency-bound chain: diagonal-block
-		// kernels + small products over <= nkb rows); the rows below it are ONE strip launch on the update's stream once the trailing
+		// kernels + small products over <= nkb rows); the rows below it are ONE strip launch on the caller's stream once the trailing
 		// update has drained -- alone on the chip, at its stand-alone speed, instead of 2 x nkb/128 sliver products beside the update.
-		// Together with the reserved mode the WHOLE chain runs on the stream masked onto the reserved CUs (no per-block hand-over).
 		const bool defer = g_potrf_strip == 3 && potrf_panel_can_strip<T>(n, r, nkb, A, lda, winv, ldp);
 		// key 21: below this many remaining rows no look-ahead at all -- the whole trailing update first, then the panel on the same
 		// stream, each alone on the chip (beside the update the chain runs 3-5x slower, and a short update cannot hide it anyway)
-		// (lab knob 31, off: serial order also in a band ABOVE the sliver threshold of the trailing update, where the update is the 128 x 128
-		// direct-to-VGPR kernel and the diagonal-block kernel beside it runs 8x slower than alone -- 265 us against 33, kernel trace of
-		// tools/potrf_only.py 16384 -- because every SIMD's fp64 ALUs are held by 64-cycle MFMAs.  Measured: it LOSES, monotonically with the band's
-		// upper edge (N = 16 384: 27.96 ms off, 28.11 / 28.67 / 29.52 / 30.09 with the edge at 11 000 / 12 000 / 14 000 / 16 500 rows; N = 32 768 179.5 ->
-		// 184.0 at 20 000): up there the update and the chain are about balanced (17 ms of update against 19 ms of chain over the first 6000 columns of
-		// N = 16 384) and the serial order gives up the update's own ramp and tail, which the chain otherwise fills.)
-		const int64_t rem_tiles = ((n - r) / IB) * ((n - r) / IB + 1) / 2;
-		const bool serial = !reserve && ((n - r) <= g_potrf_serial_below || (sizeof(T) == 8 && rem_tiles > g_gemm_sliver_tiles && (n - r) <= g_potrf_serial_band));
-		if (serial) {
+		if ((n - r) <= g_potrf_serial_below) {
 			if (r + nkb < n) {
 				const int64_t r2 = r + nkb;
-				ProfScope ps(TAG_SYRK, (double)(n - r2) * (double)(n - r2) * (double)wk, U);
+				ProfScope ps(TAG_SYRK, (double)(n - r2) * (double)(n - r2) * (double)wk, st);
 				rc = update(Pk, pre, r2, n - r2, wk, 1);
 				if (rc) return rc;
 			}
-			rc = factor_panel<T>(n, r, nkb, A, lda, winv, Pbuf[cur ^ 1], ldp, info, U, gflags);
+			rc = factor_panel<T>(n, r, nkb, A, lda, winv, Pbuf[cur ^ 1], ldp, info, st, gflags);
 			if (rc) return rc;
 			cur ^= 1;
 			k = r;
 			wk = nkb;
 			continue;
 		}
-		hipStream_t chain = (reserve && defer) ? la->diag : side;
-		HIPCHK(hipEventRecord(la->col_ready, U));
-		HIPCHK(hipStreamWaitEvent(chain, la->col_ready, 0));
-		// A short trailing update cannot hide the panel chain, and the chain's first kernel -- one workgroup that needs
-		// 83 KiB of LDS -- is slowed down by the update's workgroups once they have flooded the chip (kernel trace,
-		// tools/potrf_only.py).  Below the threshold the update therefore starts only after that kernel has run.
-		const bool diag_first = !reserve && (n - r) <= g_potrf_diag_first_below;
-		const int pflags = gflags | ((n - r - nkb) >= g_potrf_beside_min ? GEMM_BESIDE : 0);
-		rc = factor_panel<T>(n, r, nkb, A, lda, winv, Pbuf[cur ^ 1], ldp, info, chain, (reserve && defer) ? gflags : pflags, diag_first ? la->trail_done : nullptr,
-		                     (reserve && !defer) ? la->diag : nullptr, la->ev_diag, la->ev_gemm, defer ? 2 : -1);
+		HIPCHK(hipEventRecord(la->col_ready, st));
+		HIPCHK(hipStreamWaitEvent(side, la->col_ready, 0));
+		// The look-ahead panel runs BESIDE the trailing update: its panel products take the "sliver" GEMM (gemm.hip: fits into what two
+		// update workgroups leave over on a CU, so it is placed at once) instead of the tile kernels, which wait for an update workgroup
+		// to exit, or the 128 KiB one-volley kernel, which needs a CU without any update workgroup.
+		rc = factor_panel<T>(n, r, nkb, A, lda, winv, Pbuf[cur ^ 1], ldp, info, side, gflags | GEMM_BESIDE, defer ? 2 : -1);
 		if (rc) return rc;
-		HIPCHK(hipEventRecord(la->panel_done, chain));
-		if (diag_first) HIPCHK(hipStreamWaitEvent(U, la->trail_done, 0));
+		HIPCHK(hipEventRecord(la->panel_done, side));
 		if (r + nkb < n) {  // rest of the trailing matrix, lower tiles only
 			const int64_t r2 = r + nkb;
-			ProfScope ps(TAG_SYRK, (double)(n - r2) * (double)(n - r2) * (double)wk, U);      // lower triangle: m^2 k
+			ProfScope ps(TAG_SYRK, (double)(n - r2) * (double)(n - r2) * (double)wk, st);      // lower triangle: m^2 k
 			rc = update(Pk, pre, r2, n - r2, wk, 1);
 			if (rc) return rc;
 		}
-		HIPCHK(hipStreamWaitEvent(U, la->panel_done, 0));
+		HIPCHK(hipStreamWaitEvent(st, la->panel_done, 0));
 		if (defer) {
 			const int64_t mb = n - r - nkb;
-			ProfScope ps(TAG_PANEL_GEMM, (double)mb * (double)nkb * (double)nkb, U);
-			rc = trsm_strip<T>(mb, A + r * lda + r, lda, winv + (r / IB) * IB * IB, A + (r + nkb) * lda + r, lda, Pbuf[cur ^ 1] + (r + nkb) * ldp, ldp, nkb, U);
+			ProfScope ps(TAG_PANEL_GEMM, (double)mb * (double)nkb * (double)nkb, st);
+			rc = trsm_strip<T>(mb, A + r * lda + r, lda, winv + (r / IB) * IB * IB, A + (r + nkb) * lda + r, lda, Pbuf[cur ^ 1] + (r + nkb) * ldp, ldp, nkb, st);
 			if (rc) return rc;
 		}
 		// the side stream may not start overwriting workspace `cur` (panel k+2) before this
 		// trailing update has finished reading it: it waits on the next col_ready, which is
-		// recorded on `U` after this update -- stream order (and ev_mode across a change of mode) gives that.
+		// recorded on `st` after this update -- stream order gives that.
 		cur ^= 1;
 		k = r;
 		wk = nkb;
 	}
-	return switch_to(st);
+	return 0;
 }
 
-template int potf2_trtri<double>(double*, int64_t, int, double*, double*, int64_t, int32_t*, int, hipStream_t, bool);
-template int potf2_trtri<float>(float*, int64_t, int, float*, float*, int64_t, int32_t*, int, hipStream_t, bool);
+template int potf2_trtri<double>(double*, int64_t, int, double*, double*, int64_t, int32_t*, int, hipStream_t);
+template int potf2_trtri<float>(float*, int64_t, int, float*, float*, int64_t, int32_t*, int, hipStream_t);
 template int potrf<double>(int64_t, double*, int64_t, double*, double*, int, int32_t*, hipStream_t, int);
 template int potrf<float>(int64_t, float*, int64_t, float*, float*, int, int32_t*, hipStream_t, int);
 

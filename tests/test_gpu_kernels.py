@@ -1109,17 +1109,12 @@ def test_combine_and_predict_finish(L, dtype, m, n, ldo, lds):
 @pytest.mark.parametrize("n,nb", [(128, 0), (1024, 256), (2048, 512), (3200, 1024), (1000, 256), (4096, 0)])
 def test_potrf_and_trsm_beside_update(L, dtype, tol, n, nb):
 	"""STPY_FLAG_BESIDE_UPDATE routes every block of the call through the kernels that fit into what two trailing-update
-	workgroups leave over on a CU: the four-wave / 64-VGPR diagonal-block kernel and the 32 x 128 "sliver" GEMM (fp64; other
-	shapes fall back to the tile kernels).  Same factor, same inverse blocks, same solve as without the flag; the failing
+	workgroups leave over on a CU: the 32 x 128 "sliver" GEMM (fp64; other shapes fall back to the tile kernels).  Same factor, same inverse blocks, same solve as without the flag; the failing
 	pivot is reported at the same index."""
 	lib = L.load()
 	rng = np.random.RandomState(n + 5)
 	K = spd(rng, n)
-	lib.stpy_tune(11, 1 if n != 2048 else 0)          # the four-wave diagonal-block kernel is an off-by-default experiment: keep it correct
-	try:
-		Ld, winv, info = run_potrf(L, K, nb, dtype, flags=L.FLAG_BESIDE_UPDATE)
-	finally:
-		lib.stpy_tune(11, 0)
+	Ld, winv, info = run_potrf(L, K, nb, dtype, flags=L.FLAG_BESIDE_UPDATE)
 	Ld0, winv0, info0 = run_potrf(L, K, nb, dtype, flags=0)
 	assert info == 0 and info0 == 0
 	Lg = np.tril(Ld.cpu().numpy().astype(np.float64))

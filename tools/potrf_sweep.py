@@ -1,6 +1,7 @@
 """Interleaved A/B of stpy_potrf policies in ONE process (same buffers, same clocks): stpy_tune key / value pairs against
 the defaults, per matrix order.   usage: python tools/potrf_sweep.py "n1,n2,.." "key=v1|v2|..;key=..." [nb] [f32]
-e.g.  python tools/potrf_sweep.py 8192,16384,32768 "10=0|6144|1000000;7=0|8192" """
+e.g.  python tools/potrf_sweep.py 8192,16384,32768 "21=0|3200|6400;18=0|1"
+A key the loaded library does not have (stpy_tune_get = -1: retired, or an experiment knob without STPY_HIP_LIB=lab) is refused."""
 import itertools
 import sys
 import time
@@ -25,6 +26,9 @@ def main():
 	code = L.dtype_code(dt)
 	esz = 4 if dt == torch.float32 else 8
 	defaults = {k: int(lib.stpy_tune_get(k)) for k, _ in axes}
+	missing = [k for k, v in defaults.items() if v == -1]
+	if missing:
+		sys.exit("potrf_sweep: %s has no stpy_tune key %s -- the sweep would compare a no-op with itself" % (L.LIB_PATH, ", ".join(map(str, missing))))
 	for n in ns:
 		d = 16
 		x = torch.rand(n, d, dtype=dt, device=dev) * 2 - 1

@@ -204,13 +204,6 @@ if __name__ == "__main__":
 		torch.cuda.empty_cache()
 		ab_fit(6, [0, 1, 1024, 8192])
 		lib.stpy_tune(6, 1024)
-	if which == "diagfirst":
-		for n in (8192, 16384, 32768, 65536):
-			for thr in (1, 1 << 30, 1, 1 << 30):
-				lib.stpy_tune(7, thr)
-				print("diag-first below %d:" % thr, end=" ")
-				bench_potrf(n, 0)
-		lib.stpy_tune(7, 8192)
 	if which == "fixed":
 		fixed_cost()
 	if which == "leftlook":
