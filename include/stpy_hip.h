@@ -394,7 +394,9 @@ int stpy_lml_batch(int kind, int dtype, const void* x, int64_t n, int64_t ldx, i
  * Local GP experts (LocalExpertsGaussianProcess; Deisenroth and Ng 2015; the reference has no counterpart): E exact GPs on E blocks of the data
  * under ONE hyper-parameter candidate -- the arithmetic of stpy_lml_batch with the roles of data and candidate exchanged, the factor kept for
  * prediction.  One kernel term k = kappa phi (SE, MATERN12 / 32 / 52), float64 only (float32: -2); cols, inv_ls (device, d values), kappa as for
- * stpy_pchol; noise: device, ONE noise std.  The points are gathered by expert: xs (N x ldx), ys (N), offsets: device int32[E + 1], expert e owns
+ * stpy_pchol; noise: device, ONE noise std.  With cols the rows of xs AND of xt are the wide rows: coordinate k of a training point is
+ * xs[i*ldx + cols[k]], of a test point xt[t*ldt + cols[k]] (ldx, ldt above the largest entry of cols; the other columns are never read).
+ * The points are gathered by expert: xs (N x ldx), ys (N), offsets: device int32[E + 1], expert e owns
  * rows offsets[e] .. offsets[e + 1], n_e <= nmax <= stpy_experts_max_n() (512) of them.  nmax is the host's bound on n_e, by which the slices are
  * sized: an expert that violates it (info[e] = -1), or whose offsets leave [0, N] or decrease (info[e] = -2), is reported and nothing is written
  * out of bounds.  With NPM = nmax rounded up to 32, `factor` holds E slices of NPM^2 doubles (stpy_experts_factor_bytes, 16-byte aligned, owned

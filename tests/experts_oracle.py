@@ -70,6 +70,8 @@ def expert_fit(kind, x, y, inv_ls, s, kappa, weight=1.0, pidx=None, n_params=0, 
 	"""dict(L, V = L^-T, alpha, value, grad (n_params + 1: lengthscale slots, then the noise std; None without pidx)) of one expert"""
 	x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64).reshape(-1)
 	n = x.shape[0]
+	if n == 0:          # an empty expert: no evidence, no gradient, the prior
+		return dict(L=np.zeros((0, 0)), V=np.zeros((0, 0)), alpha=np.zeros(0), value=0.0, grad=None if pidx is None else np.zeros(n_params + 1), K=np.zeros((0, 0)))
 	u2 = _u2(x, x, inv_ls, cols)
 	r2 = u2.sum(axis=2)
 	K = kappa * phi(kind, r2) + s * s * np.eye(n)
@@ -91,6 +93,8 @@ def expert_fit(kind, x, y, inv_ls, s, kappa, weight=1.0, pidx=None, n_params=0, 
 
 def expert_predict(kind, x, fit, inv_ls, kappa, xt, cols=None):
 	"""(mu, var) of the latent f at xt: var = kappa - |L^-1 k*|^2"""
+	if len(fit["alpha"]) == 0:
+		return np.zeros(len(xt)), np.full(len(xt), float(kappa))
 	ks = kernel_matrix(kind, x, xt, inv_ls, kappa, cols)          # (n, M)
 	v = sla.solve_triangular(fit["L"], ks, lower=True, check_finite=False)
 	return ks.T @ fit["alpha"], kappa - np.sum(v * v, axis=0)
@@ -155,3 +159,110 @@ def reference_case(seed=5):
 	pick = np.concatenate([off[e] + np.arange(4) * 7 for e in range(len(sizes))])
 	xt = np.concatenate([xs[pick], rng.uniform(-0.2, 1.2, size=(REF["M"] - REF["M_train"], REF["d"])) + np.array([0.5, -0.25, 2.0])])
 	return dict(x=x, y=y, order=order, sizes=sizes, xs=xs, ys=ys, xt=xt, inv_ls=np.full(REF["d"], 1.0 / REF["ls"]), s=REF["s"], kappa=REF["kappa"])
+
+
+# ------------------------------------------------------------------------------------------------ the mixed-size case of the GPU tests
+# one expert per regime of the kernels (blocks of 32 rows, rounds of 64, the cap of 512); all but the last have NP_e < NPM = 512
+BORDER = dict(sizes=[1, 31, 32, 33, 63, 64, 65, 96, 97, 128, 129, 200, 511, 512], d=5, shift=(0.5, -0.25, 2.0, 10.0, -3.0),
+			  ls=(0.4, 0.7, 0.3, 0.9, 0.5), s=0.1, kappa=1.3, M=97, far=40.0)
+
+
+def border_case(seed=17):
+	"""xs (1962, 5), gathered by expert, in the unit cube shifted off-centre; ys as in reference_case; 97 test points: two training points of every
+	expert (its first and its last row; one for the one-point expert), 69 uniform in the cube widened by 0.2, and one 40 units away along every
+	axis, where every expert returns the prior"""
+	B = BORDER
+	rng = np.random.RandomState(seed)
+	sizes, d, shift = list(B["sizes"]), B["d"], np.array(B["shift"])
+	N = sum(sizes)
+	xs = rng.uniform(0.0, 1.0, size=(N, d)) + shift
+	ys = np.sin(4.0 * xs[:, 0]) * np.cos(3.0 * xs[:, 1]) + 0.5 * xs[:, 2] + 0.1 * rng.normal(size=N)
+	off = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+	pick = np.concatenate([[off[e]] if sizes[e] == 1 else [off[e], off[e + 1] - 1] for e in range(len(sizes))])
+	free = rng.uniform(-0.2, 1.2, size=(B["M"] - len(pick) - 1, d)) + shift
+	xt = np.concatenate([xs[pick], free, (shift + B["far"])[None, :]])
+	return dict(xs=xs, ys=ys, sizes=sizes, offsets=off, xt=xt, pick=pick, inv_ls=1.0 / np.array(B["ls"]), s=B["s"], kappa=B["kappa"])
+
+
+# ------------------------------------------------------------------------------------------------ one expert again, in extended precision
+# The formulas of expert_fit / expert_predict restated with plain loops in np.longdouble (x87: 64-bit mantissa, eps 1.1e-19), or, where long double
+# is no wider than double, in mpmath numbers of 80 bits held in object arrays: the yardstick of the float64 oracle above.
+_LD = bool(np.finfo(np.longdouble).eps < 2e-19)
+
+
+def _hp(a):
+	"""float64 data -> the extended type, exactly"""
+	a = np.asarray(a, dtype=np.float64)
+	if _LD:
+		return a.astype(np.longdouble)
+	import mpmath
+	mpmath.mp.prec = 80
+	return np.frompyfunc(mpmath.mpf, 1, 1)(a) if a.ndim else mpmath.mpf(float(a))
+
+
+def _hp_fn(name):
+	if _LD:
+		return getattr(np, name)
+	import mpmath
+	return np.frompyfunc(getattr(mpmath, name), 1, 1)
+
+
+def _hp_phi(kind, r2, derivative=False):
+	sqrt, exp = _hp_fn("sqrt"), _hp_fn("exp")
+	r, s3, s5 = sqrt(r2), sqrt(_hp(3.0)), sqrt(_hp(5.0))
+	if kind == SE:
+		return exp(-r2 / 2)
+	if kind == MATERN12:
+		if not derivative:
+			return exp(-r)
+		pos = (r > 0).astype(bool)          # (coincident points: F = 0, as in dfactor)
+		return np.where(pos, exp(-r) / np.where(pos, r, 1), 0 * r)
+	if kind == MATERN32:
+		return 3 * exp(-s3 * r) if derivative else (1 + s3 * r) * exp(-s3 * r)
+	return (_hp(5.0) / 3) * (1 + s5 * r) * exp(-s5 * r) if derivative else (1 + s5 * r + 5 * r2 / 3) * exp(-s5 * r)
+
+
+def expert_extended(kind, x, y, inv_ls, s, kappa, weight=1.0, pidx=None, n_params=0, cols=None, xt=None):
+	"""dict(alpha, value, grad (or None), mu, var (with xt)) of one expert, every entry in the extended type: Gram matrix from direct differences,
+	column Cholesky, forward substitution of [y | k* | I], back substitution for alpha, K^-1 = W^T W for the gradient.  n = 512: about a second"""
+	cols = list(range(len(inv_ls))) if cols is None else list(cols)
+	x, y, il = _hp(np.asarray(x, dtype=np.float64)[:, cols]), _hp(np.asarray(y, dtype=np.float64).reshape(-1)), _hp(inv_ls)
+	kap, sd, w = _hp(kappa), _hp(s), _hp(weight)
+	n, log = x.shape[0], _hp_fn("log")
+	u2 = ((x[:, None, :] - x[None, :, :]) * il[None, None, :]) ** 2
+	r2 = u2.sum(axis=2)
+	K = kap * _hp_phi(kind, r2) + sd * sd * _hp(np.eye(n))
+	L = 0 * K
+	for j in range(n):
+		L[j, j] = _hp_fn("sqrt")(K[j, j] - L[j, :j] @ L[j, :j])
+		L[j + 1:, j] = (K[j + 1:, j] - L[j + 1:, :j] @ L[j, :j]) / L[j, j]
+	rhs = [y[:, None]]
+	if xt is not None:
+		t = _hp(np.asarray(xt, dtype=np.float64)[:, cols])
+		ks = kap * _hp_phi(kind, (((x[:, None, :] - t[None, :, :]) * il[None, None, :]) ** 2).sum(axis=2))
+		rhs.append(ks)
+	if pidx is not None:
+		rhs.append(_hp(np.eye(n)))
+	B = np.concatenate(rhs, axis=1)
+	for j in range(n):          # forward substitution, all right-hand sides at once
+		B[j] = (B[j] - L[j, :j] @ B[:j]) / L[j, j]
+	z = B[:, 0]
+	alpha = z.copy()
+	for j in range(n - 1, -1, -1):          # back substitution
+		alpha[j] = (alpha[j] - L[j + 1:, j] @ alpha[j + 1:]) / L[j, j]
+	out = dict(alpha=alpha, value=(z @ z) / 2 + w * log(np.diagonal(L)).sum(), grad=None)
+	at = 1
+	if xt is not None:
+		v = B[:, 1:1 + ks.shape[1]]
+		out["mu"], out["var"] = ks.T @ alpha, kap - (v * v).sum(axis=0)
+		at += ks.shape[1]
+	if pidx is not None:
+		W = B[:, at:]
+		Kinv = W.T @ W
+		H = (w * Kinv - alpha[:, None] * alpha[None, :]) * kap * _hp_phi(kind, r2, derivative=True)
+		g = [0 * kap for _ in range(n_params + 1)]
+		for k, p in enumerate(pidx):
+			g[int(p)] = g[int(p)] + (H * u2[:, :, k]).sum() * il[k] / 2
+		g[n_params] = sd * (w * np.trace(Kinv) - alpha @ alpha)
+		out["grad"] = np.array(g)
+	return out

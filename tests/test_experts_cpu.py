@@ -1,6 +1,7 @@
 """
 Local GP experts, the parts that need no GPU: the NumPy oracle (tests/experts_oracle.py) against oracle/gp_oracle.py and central differences, the
-combination identities, the distance of the GPU tests' reference case from the combination's clamp, the host side of
+combination identities, the distance of the GPU tests' reference case from the combination's clamp, the float64 oracle against an
+extended-precision restatement on the GPU tests' mixed-size case (experts of 1 .. 512 points), the host side of
 LocalExpertsGaussianProcess with the device out of reach, the argument checks of the C entry points (every refusal comes before the first HIP
 call, so placeholder pointers are safe), and the resource usage of the kernels.
 """
@@ -145,6 +146,64 @@ def test_reference_case_is_far_from_the_clamp(kind):
 		B[j] = (B[j] - Lc[j, :j] @ B[:j]) / Lc[j, j]
 	var_x = kap - (B[:, 1:] ** 2).sum(axis=0)
 	assert float(np.max(np.abs(o["var_e"][0] - var_x))) <= 1e-12 * r["kappa"]
+
+
+@pytest.mark.parametrize("kind", XO.KINDS)
+def test_border_case_oracle_against_extended_precision(kind):
+	"""The mixed-size case of the GPU tests (sizes 1 .. 512, one per regime of the kernels): the float64 oracle against the restatement in extended
+	precision (XO.expert_extended), every expert, with the scaling of the GPU tests' _close.  The bound is their TOL / 100 = 1e-10: rounding of
+	the float64 solves is about eps cond(K_e), cond(K_e) <= 1 + kappa n / s^2 = 6.7e4 at the cap (measured: 1e3 .. 2e4), so 1e-11 at the worst.
+	Measured (alpha / mu / var / value / gradient row; largest cond(K_e); min var_e / kappa):
+	SE         4.5e-13 / 6.9e-14 / 8.0e-15 / 1.4e-14 / 2.1e-13; 1.7e4; 1.7e-3
+	Matern 1/2 1.2e-14 / 2.2e-15 / 9.8e-16 / 4.9e-14 / 5.2e-16; 1.2e3; 7.5e-3
+	Matern 3/2 4.8e-14 / 1.1e-14 / 1.9e-15 / 7.1e-16 / 3.3e-15; 9.6e3; 6.9e-3
+	Matern 5/2 2.3e-13 / 2.5e-14 / 3.0e-15 / 4.4e-15 / 9.7e-14; 1.4e4; 6.0e-3"""
+	c = XO.border_case()
+	B = XO.BORDER
+	assert c["sizes"] == B["sizes"] and sum(c["sizes"]) == 1962 and max(c["sizes"]) == 512 and c["xt"].shape == (97, 5)
+	n_train = len(c["pick"])
+	assert n_train == 27 and np.array_equal(c["xt"][:n_train], c["xs"][c["pick"]])
+	assert not any(np.any(np.all(c["xs"] == t, axis=1)) for t in c["xt"][n_train:])
+	pidx = list(range(B["d"]))
+	o = XO.experts(kind, c["xs"], c["ys"], c["sizes"], c["inv_ls"], c["s"], c["kappa"], 0.7, pidx, B["d"], xt=c["xt"])
+	# nothing near the clamp, as on the reference case
+	assert XO.n_clamped(o["var_e"], c["kappa"]) == 0
+	lo = float(o["var_e"].min() / c["kappa"])
+	assert lo > 1e-3, lo
+	# the far point: the prior, from every expert
+	assert np.all(np.abs(o["mu_e"][:, -1]) < 1e-30) and np.all(o["var_e"][:, -1] == c["kappa"])
+	off = c["offsets"]
+	x = [XO.expert_extended(kind, c["xs"][off[e]:off[e + 1]], c["ys"][off[e]:off[e + 1]], c["inv_ls"], c["s"], c["kappa"], 0.7, pidx, B["d"], xt=c["xt"])
+		 for e in range(len(c["sizes"]))]
+	f64 = lambda a: np.asarray(a, dtype=np.float64)
+	alpha_x, mu_x = np.concatenate([f["alpha"] for f in x]), np.array([f["mu"] for f in x])
+	err = dict(alpha=np.max(np.abs(f64(o["alpha"] - alpha_x))) / np.max(np.abs(f64(alpha_x))),
+			   mu=np.max(np.abs(f64(o["mu_e"] - mu_x))) / np.max(np.abs(f64(mu_x))),
+			   var=np.max(np.abs(f64(o["var_e"] - np.array([f["var"] for f in x])))) / c["kappa"],
+			   value=max(abs(float(o["value"][e] - f["value"])) / abs(float(f["value"])) for e, f in enumerate(x)),
+			   grad=max(np.max(np.abs(f64(o["grad"][e] - f["grad"]))) / np.max(np.abs(f64(f["grad"]))) for e, f in enumerate(x)))
+	print("kind", kind, "min var_e / kappa", lo, "cond", max(float(np.linalg.cond(f["K"])) for f in o["fits"]), {k: float(v) for k, v in err.items()})
+	assert all(v <= 1e-10 for v in err.values()), err
+
+
+def test_extended_precision_fallback_agrees():
+	"""the mpmath route of XO.expert_extended (taken where long double is no wider than double) against the long-double one, on a small expert"""
+	c = XO.border_case()
+	a, b = int(c["offsets"][3]), int(c["offsets"][4])
+	args = (c["xs"][a:b], c["ys"][a:b], c["inv_ls"], c["s"], c["kappa"], 0.7, [0, 1, 2, 3, 4], 5)
+	if not XO._LD:
+		pytest.skip("long double is no wider than double here: the mpmath route is the one the test above took")
+	for kind in XO.KINDS:
+		ld = XO.expert_extended(kind, *args, xt=c["xt"][:9])
+		XO._LD = False
+		try:
+			mp = XO.expert_extended(kind, *args, xt=c["xt"][:9])
+		finally:
+			XO._LD = True
+		for key in ("alpha", "mu", "var", "grad"):
+			d = np.max(np.abs(np.asarray(ld[key], dtype=np.float64) - np.asarray(mp[key], dtype=np.float64)))
+			assert d <= 1e-13 * np.max(np.abs(np.asarray(ld[key], dtype=np.float64))), (kind, key, d)
+		assert abs(float(ld["value"]) - float(mp["value"])) <= 1e-13 * abs(float(ld["value"]))
 
 
 # --------------------------------------------------------------------------------------------- 4. host behaviour without the device
