@@ -641,6 +641,9 @@ int stpy_kmv_dxx(int kind, int dtype, const void* a, int64_t n, int64_t lda, con
  * For the mean gradient alpha = K^-1 y; for the variance gradient Wt = K* K^-1 (stpy_trsm_right_ln).  alpha or Wt may be
  * NULL (not both); u / v NULL mean 1.  kind, cols, inv_ls, kappa, offset as stpy_gram (the dot-product kinds differentiate
  * kappa phi(<xt, x_i> scaled)); the kernel values are recomputed from the points by direct differences, K* is not read.
+ * The coordinates are subtracted BEFORE they are scaled by inv_ls: a translate of x and xt that keeps their differences exact
+ * gives the same bits, and a test point equal to a training point has e == 0 exactly (that pair adds exactly 0 to G, also for
+ * MATERN12, whose phi'(r) / r is taken as 0 at r == 0).
  * combine: STPY_OUT_SET or STPY_OUT_ADD (the terms of a sum accumulate); cols must not repeat a column.  order 2 is refused
  * for MATERN12 / MATERN32 (no Hessian at r = 0).  The n range is split into chunks whose partial sums land in `work`
  * (stpy_gram_grad_workspace_bytes(dtype, m, n, d, order) bytes) and are summed in a fixed order: results are bit-identical

@@ -15,7 +15,17 @@
 //     grid dimension) and recomputes r for each -- any d is accepted, the points are read through L1 (they are
 //     tiny next to Wt), nothing scales with d in registers or LDS;
 //   * the distances are DIRECT differences (xt - x_i) * inv_ls, never the norm expansion: the derivatives need the
-//     small differences accurately and Matern 1/2 needs exact zeros;
+//     small differences accurately and Matern 1/2 needs exact zeros.  The raw coordinates are subtracted BEFORE the
+//     difference is scaled (as kmv.hip, kmv_pair.h, lb_block.h and reduce.hip do): scaling first rounds x * inv_ls at
+//     the magnitude of the data's offset from the origin and loses (offset / spread) eps; subtracting first, a
+//     translate of the data by a vector that keeps the differences exact gives the same bits (and a coincident pair
+//     has e = 0 exactly: x * inv_ls - x * inv_ls, contracted into one fma, leaves the rounding residual of the product,
+//     which Matern 1/2 then divides by).  The dot-product kinds are not translation invariant and keep the product of
+//     the two scaled coordinates.  The first derivatives sum w1 * (xt - x_i) of the RAW difference and take both
+//     factors inv_ls_k after the sum (one multiply per output and pair less than scaling inside the loop); the
+//     Hessian's products e_k e_l are scaled inside the loop.  Subtracting first costs the distance loop one multiply
+//     per coordinate and pair that xt * inv_ls - x_i * inv_ls hid in an fma (12.0 against 10.4 ms at the headline
+//     shape); with ONE lengthscale for all coordinates r^2 is inv_ls^2 sum (xt - x_i)^2 and the multiply is gone again;
 //   * the workgroup's lanes are summed through LDS in a fixed tree, the chunks (split over n so that small m still
 //     fills the chip) land in the workspace and a second kernel sums them in chunk order: the result is bit-identical
 //     from run to run (no atomics anywhere), and the final scaling by inv_ls and the scatter into the term's columns
@@ -76,6 +86,10 @@ void gram_grad_kernel(GradArgs<T> p)
 	const int tid = threadIdx.x;
 	const bool dot = (p.kind == STPY_K_LINEAR || p.kind == STPY_K_POLY);
 	const int64_t i_end = min(p.n, (int64_t)(split + 1) * p.chunk);
+	// one lengthscale for every coordinate (the isotropic kernels): r^2 = inv_ls^2 sum (xt - x_i)^2, the scaling once per pair, not per coordinate
+	const T il0 = p.inv_ls[0];
+	bool iso = !dot;
+	for (int k = 1; k < p.d; ++k) iso = iso && p.inv_ls[k] == il0;
 
 	int64_t trow[GG_TM];
 #pragma unroll
@@ -84,11 +98,12 @@ void gram_grad_kernel(GradArgs<T> p)
 #pragma unroll
 	for (int t = 0; t < GG_TM; ++t) { us[t] = p.u ? p.u[trow[t]] : T(1); vs[t] = p.v ? p.v[trow[t]] : T(1); }
 
-	// the block's scaled test coordinates (first-derivative outputs): read from LDS inside the loop, not held in registers
+	// the block's raw test coordinates (first-derivative outputs): read from LDS inside the loop, not held in registers.  The dot-product
+	// kinds, whose factor is x_i alone, hold 0 there: one form w1 * (xq - x_i) serves both, and the finish kernel flips their sign
 	__shared__ T xq[GG_TM][GG_QB];
 	if (tid < GG_TM * GG_QB) {
 		const int t = tid / GG_QB, q = q0 + tid % GG_QB;
-		xq[t][tid % GG_QB] = q < p.d ? p.xt[min(t0 + t, p.m - 1) * p.ldt + (p.cols ? p.cols[q] : q)] * p.inv_ls[q] : T(0);
+		xq[t][tid % GG_QB] = (q < p.d && !dot) ? p.xt[min(t0 + t, p.m - 1) * p.ldt + (p.cols ? p.cols[q] : q)] : T(0);
 	}
 	__syncthreads();
 
@@ -100,19 +115,30 @@ void gram_grad_kernel(GradArgs<T> p)
 
 	for (int64_t i = (int64_t)split * p.chunk + tid; i < i_end; i += GG_THREADS) {
 		const T* xi = p.x + i * p.ldx;
-		// ---- squared scaled distance (stationary) or scaled inner product (dot-product kinds), direct differences
+		// ---- squared scaled distance (stationary: subtract, then scale) or scaled inner product (dot-product kinds)
 		T s[GG_TM];
 #pragma unroll
 		for (int t = 0; t < GG_TM; ++t) s[t] = T(0);
-		for (int k = 0; k < p.d; ++k) {
-			const int c = p.cols ? p.cols[k] : k;
-			const T il = p.inv_ls[k];
-			const T a = xi[c] * il;
+		if (iso) {
+			for (int k = 0; k < p.d; ++k) {
+				const int c = p.cols ? p.cols[k] : k;
+				const T a = xi[c];
 #pragma unroll
-			for (int t = 0; t < GG_TM; ++t) {
-				const T b = p.xt[trow[t] * p.ldt + c] * il;
-				if (dot) s[t] += a * b;
-				else { const T e = b - a; s[t] += e * e; }
+				for (int t = 0; t < GG_TM; ++t) { const T e = p.xt[trow[t] * p.ldt + c] - a; s[t] += e * e; }
+			}
+#pragma unroll
+			for (int t = 0; t < GG_TM; ++t) s[t] = (s[t] * il0) * il0;
+		} else {
+			for (int k = 0; k < p.d; ++k) {
+				const int c = p.cols ? p.cols[k] : k;
+				const T il = p.inv_ls[k];
+				const T a = xi[c];
+#pragma unroll
+				for (int t = 0; t < GG_TM; ++t) {
+					const T b = p.xt[trow[t] * p.ldt + c];
+					if (dot) s[t] += (a * il) * (b * il);
+					else { const T e = (b - a) * il; s[t] += e * e; }
+				}
 			}
 		}
 		// ---- coefficient and the two radial factors: first derivatives w1 * e_k, second w2 * e_k e_l (+ w1 on the diagonal)
@@ -153,21 +179,20 @@ void gram_grad_kernel(GradArgs<T> p)
 			if (HESS && q >= p.d) { ka = (q - p.d) / p.d; kb = (q - p.d) - ka * p.d; }
 			const int ca = p.cols ? p.cols[ka] : ka;
 			const T ila = p.inv_ls[ka];
-			const T xa = xi[ca] * ila;
+			const T xa = xi[ca];
 			if (kb < 0) {
 #pragma unroll
 				for (int t = 0; t < GG_TM; ++t) {
-					const T ea = dot ? xa : xq[t][qq] - xa;
-					acc[t][qq] += w1[t] * ea;
+					acc[t][qq] += w1[t] * (xq[t][qq] - xa);                 // (raw difference: both factors inv_ls in the finish kernel)
 				}
 			} else if (HESS) {
 				const int cb = p.cols ? p.cols[kb] : kb;
 				const T ilb = p.inv_ls[kb];
-				const T xb = xi[cb] * ilb;
+				const T xb = xi[cb];
 #pragma unroll
 				for (int t = 0; t < GG_TM; ++t) {
-					const T ea = dot ? xa : p.xt[trow[t] * p.ldt + ca] * ila - xa;
-					const T eb = dot ? xb : p.xt[trow[t] * p.ldt + cb] * ilb - xb;
+					const T ea = dot ? xa * ila : (p.xt[trow[t] * p.ldt + ca] - xa) * ila;
+					const T eb = dot ? xb * ilb : (p.xt[trow[t] * p.ldt + cb] - xb) * ilb;
 					acc[t][qq] += w2[t] * ea * eb + ((!dot && ka == kb) ? w1[t] : T(0));
 				}
 			}
@@ -198,11 +223,12 @@ void gram_grad_kernel(GradArgs<T> p)
 	}
 }
 
-// chunk partial sums in chunk order, the inv_ls scaling of the raw coordinates, the scatter into the term's columns
+// chunk partial sums in chunk order, the inv_ls factors left to the end (first derivatives: the one of the scaled difference and
+// the one of the chain rule; second derivatives: the two of the chain rule), the scatter into the term's columns
 template <typename T>
 __global__ __launch_bounds__(256)
 void gram_grad_finish_kernel(const T* __restrict__ part, int nsplit, int64_t m, int Q, int d, const int32_t* cols, const T* __restrict__ inv_ls,
-                             int combine, T* G, int64_t ldg, T* H)
+                             int combine, T* G, int64_t ldg, T* H, int negate_g)
 {
 	const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
 	if (idx >= m * Q) return;
@@ -212,7 +238,8 @@ void gram_grad_finish_kernel(const T* __restrict__ part, int nsplit, int64_t m, 
 	for (int sp = 0; sp < nsplit; ++sp) s += part[((int64_t)sp * m + t) * Q + q];
 	T* o;
 	if (q < d) {
-		s *= inv_ls[q];
+		s = (s * inv_ls[q]) * inv_ls[q];
+		if (negate_g) s = -s;                  // dot-product kinds: the sum ran over w1 * (0 - x_i)
 		o = G + t * ldg + (cols ? cols[q] : q);
 	} else {
 		const int ka = (q - d) / d, kb = (q - d) - ka * d;
@@ -255,7 +282,8 @@ int gram_grad(int kind, const T* x, int64_t n, int64_t ldx, const T* xt, int64_t
 	int rc = check_launch("stpy_gram_grad");
 	if (rc) return rc;
 	hipLaunchKernelGGL((gram_grad_finish_kernel<T>), dim3((unsigned)((m * Q + 255) / 256)), dim3(256), 0, st,
-	                   (const T*)work, nsplit, m, Q, d, cols, inv_ls, combine, G, ldg, H);
+	                   (const T*)work, nsplit, m, Q, d, cols, inv_ls, combine, G, ldg, H,
+	                   (int)(p.kind == STPY_K_LINEAR || p.kind == STPY_K_POLY));
 	return check_launch("stpy_gram_grad finish");
 }
 
