@@ -421,11 +421,31 @@ int stpy_lml_batch(int kind, int dtype, const void* x, int64_t n, int64_t ldx, i
  * stpy_experts_combine: one thread per test point, sums over experts in expert order; each var_e is first clamped to [kappa 2^-52, kappa];
  * with c_e = 1 / var_e:   mode 0 PoE: beta_e = 1;  1 gPoE: beta_e = 1 / E;  2 BCM: beta_e = 1;  3 rBCM: beta_e = 1/2 (log kappa - log var_e);
  *   1 / var = sum beta_e c_e  (+ (1 - E) / kappa for BCM, + (1 - sum beta_e) / kappa for rBCM),   mu = var * sum beta_e c_e mu_e
+ * stpy_experts_predict_grad: stpy_experts_predict with the input gradients of every expert's mean and variance, same grid, one launch.  mu_e and
+ * var_e carry the bits stpy_experts_predict writes (the two kernels call one body).  The gradients are compact arrays over the SELECTED
+ * coordinates, in cols order: entry (e, t, m) at e*lde + t*ldg + m, m < d, ldg >= d, lde >= M*ldg.  With F the derivative factor of the term
+ * (d k / d r^2 = -kappa F / 2: SE exp(-r^2/2), Matern 1/2 exp(-r)/r, 3/2 3 exp(-sqrt3 r), 5/2 5/3 (1 + sqrt5 r) exp(-sqrt5 r)), il = inv_ls
+ * and w = K_e^-1 k* = L_e^-T (L_e^-1 k*), the second triangular product on the fp64 MFMA as the first:
+ *   gmu_e[e, t, m]     = -kappa il_m^2 sum_k alpha_k F_tk (xt_m - x_km)
+ *   gvar_e[e, t, m]    = 2 kappa il_m^2 sum_k w_tk F_tk (xt_m - x_km)          (d k(x, x) / dx = 0: the term is stationary)
+ * from direct coordinate differences, subtracted before they are scaled.  Matern 1/2 on a coincident pair (r = 0 exactly) contributes zero, the
+ * convention of stpy_gram_grad.  An expert with info[e] != 0 yields mu_e = 0, var_e = kappa and zero gradients.  Rows t >= M are never written.
+ * `work`: TWO slices of 32 NPM doubles per expert and tile (the k* tile, over which w is written, and L_e^-1 k*): twice the bytes of the
+ * prediction's query.
+ * stpy_experts_combine_grad: stpy_experts_combine (the same bits in mu and var) with the chain rule on top, one thread per test point, experts in
+ * expert order.  Per selected coordinate, with v_e = clamp(var_e), c_e = 1 / v_e:
+ *   dv_e    = gvar_e where kappa 2^-52 <= var_e <= kappa, else 0: the derivative of the function as implemented; on the ties var_e == kappa and
+ *             var_e == kappa 2^-52 the clamp counts as inactive
+ *   dc_e    = -c_e^2 dv_e;   dbeta_e = -dv_e / (2 v_e) for rBCM, 0 otherwise
+ *   dprec   = sum (dbeta_e c_e + beta_e dc_e)  (- sum dbeta_e / kappa for rBCM);   dwm = sum [(dbeta_e c_e + beta_e dc_e) mu_e + beta_e c_e gmu_e]
+ *   dvar    = -var^2 dprec;   dmu[t*ldo + m] = dvar wm + var dwm  (wm = sum beta_e c_e mu_e);   dstd[t*ldo + m] = dvar / (2 sqrt(var)),  ldo >= d
+ * It reads nothing but its arguments: a pure function of (mode, mu_e, var_e, gmu_e, gvar_e, kappa).
  * Every sum has a fixed order, there are no atomics, spin-waits or cooperative grids, no host synchronisation and no allocation: two calls are
  * bit-identical, and an expert's outputs are bit-identical wherever it sits in whatever batch.
  * Refused before any HIP call: kind (-1), dtype (-2), a NULL array (-3; cols may be NULL, grad may be NULL, pidx with it), nmax above the cap (-4),
  * ldx or ldt < d (-5), d < 1 (-6), N / E / M out of range (-9), combine mode (-10), kappa not positive and finite (-11), ldm < M (-13), np < 1
- * with a gradient (-16), ldg < np + 1 (-19), work_bytes below the query (-20), misalignment (-21), factor_bytes below its query (-22).
+ * with a gradient (-16), ldg < np + 1 (fit) or ldg < d, ldo < d, lde < M*ldg (the input gradients) (-19), work_bytes below the query (-20),
+ * misalignment (-21), factor_bytes below its query (-22).
  * E == 0, N == 0 (or M == 0): returns 0, nothing is read or written.
  */
 int64_t stpy_experts_max_n(void);
@@ -446,6 +466,17 @@ int stpy_experts_predict(int kind, int dtype, const void* xs, int64_t N, int64_t
                          void* work, int64_t work_bytes, void* stream);
 int stpy_experts_combine(int mode, int64_t E, int64_t M, const void* mu_e, const void* var_e, int64_t ldm, double kappa,
                          void* mu, void* var, void* stream);
+int64_t stpy_experts_predict_grad_workspace_bytes(int dtype, int64_t nmax, int d, int64_t E, int64_t M);
+int stpy_experts_predict_grad(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols,
+                              const int32_t* offsets, int64_t E, int64_t nmax, const void* inv_ls, double kappa,
+                              const void* factor, int64_t factor_bytes, const void* alpha, const int32_t* info,
+                              const void* xt, int64_t M, int64_t ldt,
+                              void* mu_e, void* var_e, int64_t ldm,
+                              void* gmu_e, void* gvar_e, int64_t ldg, int64_t lde,
+                              void* work, int64_t work_bytes, void* stream);
+int stpy_experts_combine_grad(int mode, int64_t E, int64_t M, int d, const void* mu_e, const void* var_e, int64_t ldm,
+                              const void* gmu_e, const void* gvar_e, int64_t ldg, int64_t lde, double kappa,
+                              void* mu, void* var, void* dmu, void* dstd, int64_t ldo, void* stream);
 
 /*
  * Greedy pivoted partial Cholesky of the kernel matrix K_il = kappa phi(|(x_i - x_l)[cols] o inv_ls|), columns generated on the fly: the landmark

@@ -77,6 +77,10 @@ SIGNATURES = {
 	"stpy_experts_predict": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
 							 _vp, _i64, _vp]),
 	"stpy_experts_combine": (_i32, [_i32, _i64, _i64, _vp, _vp, _i64, _dbl, _vp, _vp, _vp]),
+	"stpy_experts_predict_grad_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64, _i64]),
+	"stpy_experts_predict_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
+								  _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
+	"stpy_experts_combine_grad": (_i32, [_i32, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _dbl, _vp, _vp, _vp, _vp, _i64, _vp]),
 	"stpy_pchol_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_pchol": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _i64, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 	"stpy_kmv_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i64]),
@@ -512,6 +516,45 @@ def experts_predict(kind, xs, offsets, nmax, inv_ls, kappa, factor, alpha, info,
 def experts_combine(mode, mu_e, var_e, kappa, mu, var):
 	"""mu, var (M,) from the experts' (E, M) predictions: mode 0 PoE, 1 gPoE, 2 BCM, 3 rBCM (stpy_experts_combine in the header)."""
 	_launch("stpy_experts_combine", int(mode), mu_e.shape[0], mu_e.shape[1], ptr(mu_e), ptr(var_e), ld(mu_e), float(kappa), ptr(mu), ptr(var))
+
+
+def _grad_strides(g):
+	"""(ldg, lde) of an (E, M, d) gradient array with unit last stride, which may be a view: row and expert stride in elements (a dimension of
+	one entry may report any stride: it gets the dense one)."""
+	E, M, d = g.shape
+	if d > 1 and g.stride(2) != 1:
+		raise StpyHipError("experts gradients: the last dimension must be contiguous")
+	ldg = g.stride(1) if M > 1 else max(g.stride(1), d, 1)
+	return ldg, (g.stride(0) if E > 1 else max(g.stride(0), M * ldg, 1))
+
+
+def experts_predict_grad_workspace(nmax, d, E, M, like):
+	"""Scratch of stpy_experts_predict_grad (dead after the call; one buffer can serve several launches of at most these sizes)."""
+	return _work(max(int(load().stpy_experts_predict_grad_workspace_bytes(F64, int(nmax), d, E, M)), 16), like)
+
+
+def experts_predict_grad(kind, xs, offsets, nmax, inv_ls, kappa, factor, alpha, info, xt, mu_e, var_e, gmu_e, gvar_e, cols=None, work=None):
+	"""experts_predict plus the input gradients gmu_e, gvar_e (E, M, d) of every expert's mean and latent variance over the selected coordinates,
+	one launch (stpy_experts_predict_grad in the header); mu_e and var_e carry the bits of experts_predict."""
+	N, d, E, M = xs.shape[0], _ncols(xs, cols), offsets.numel() - 1, xt.shape[0]
+	if work is None:
+		work = experts_predict_grad_workspace(nmax, d, E, M, xs)
+	ldg, lde = _grad_strides(gmu_e)
+	if (ldg, lde) != _grad_strides(gvar_e):
+		raise StpyHipError("experts_predict_grad: gmu_e and gvar_e must share their strides")
+	_launch("stpy_experts_predict_grad", kind, dtype_code(xs.dtype), ptr(xs), N, ld(xs), d, ptr(cols), ptr(offsets), E, int(nmax), ptr(inv_ls), float(kappa),
+			ptr(factor), factor.numel(), ptr(alpha), ptr(info), ptr(xt), M, ld(xt), ptr(mu_e), ptr(var_e), ld(mu_e), ptr(gmu_e), ptr(gvar_e), ldg, lde,
+			ptr(work), work.numel())
+
+
+def experts_combine_grad(mode, mu_e, var_e, gmu_e, gvar_e, kappa, mu, var, dmu, dstd):
+	"""experts_combine plus dmu, dstd (M, d): the input gradients of the combined mean and standard deviation by the chain rule through the
+	combination, its clamp and rBCM's weights (stpy_experts_combine_grad in the header)."""
+	ldg, lde = _grad_strides(gmu_e)
+	if (ldg, lde) != _grad_strides(gvar_e) or ld(dmu) != ld(dstd):
+		raise StpyHipError("experts_combine_grad: gmu_e / gvar_e and dmu / dstd must share their strides")
+	_launch("stpy_experts_combine_grad", int(mode), mu_e.shape[0], mu_e.shape[1], gmu_e.shape[2], ptr(mu_e), ptr(var_e), ld(mu_e), ptr(gmu_e), ptr(gvar_e),
+			ldg, lde, float(kappa), ptr(mu), ptr(var), ptr(dmu), ptr(dstd), ld(dmu))
 
 
 def pchol(kind, x, inv_ls, m, cols=None, kappa=1.0, tol=0.0, ldf=None):

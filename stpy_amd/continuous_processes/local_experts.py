@@ -13,14 +13,22 @@ What runs where
   per-expert Gram fill, Cholesky, L^-T, alpha, evidence, gradient     stpy_experts_fit      (csrc/experts.hip; one workgroup per expert)
   per-expert mean and latent variance at the test points              stpy_experts_predict  (one workgroup per expert and 32 test points)
   combination over experts                                            stpy_experts_combine  (one thread per test point)
+  the same two with input gradients (mean_std_grad, ucb_optimize):
+    per-expert mean, variance and their gradients, w = K_e^-1 k*      stpy_experts_predict_grad  (same grid; two triangular MFMA products)
+    combination and its chain rule (clamp, rBCM's weights)            stpy_experts_combine_grad  (one thread per test point)
 Python partitions (numpy, host), gathers the points by expert (one device index_select), sequences those launches and owns the tensors.
 
 The hyper-parameters are shared by all experts; the kernel is ONE stationary term (SE / Matern 1/2, 3/2, 5/2, isotropic or ARD, on a column
 group or on all columns), float64 only.  Variances are those of the latent f (no noise term), as in the dense class; like every ``mean_std`` /
 ``mean_var`` of the package the second return value is a standard deviation.
 
-Out of scope (refused with the reason): input gradients and ``ucb_optimize``, spatial partitions beyond a user-given assignment, appending and
-deleting points, float32, an explicit ``Sigma``, composite kernels, several GPUs.
+``mean_std_grad`` returns the input gradients of the combined mean and standard deviation -- of the function ``mean_std`` computes, clamp and
+rBCM weights included -- and ``ucb_optimize`` climbs the acquisition from all its starts as one stacked L-BFGS-B problem, two launches per
+evaluation and chunk.
+
+Out of scope (refused with the reason): autograd through a test tensor with ``requires_grad`` (use ``mean_std_grad``), ``ucb_optimize`` before a
+fit, spatial partitions beyond a user-given assignment, appending and deleting points, float32, an explicit ``Sigma``, composite kernels,
+several GPUs.
 """
 import numpy as np
 import torch
@@ -87,9 +95,11 @@ class _ExpertsEvidenceFn(torch.autograd.Function):
 class LocalExpertsGaussianProcess(Estimator):
 
 	def __init__(self, gamma=1, s=0.001, kappa=1., kernel_name="squared_exponential", d=1, kernel=None, nu=1.5, expert_size=256,
-				 partition="random", partition_seed=0, combine="rbcm", max_size=10000):
+				 partition="random", partition_seed=0, combine="rbcm", max_size=10000, bounds=None):
 		self.s = s
 		self.d = d
+		self.bounds = bounds                             # box of ucb_optimize: a (low, high) per coordinate
+		self.optimize_info = None
 		self.x = self.y = None
 		self.n = 0
 		self.fitted = False
@@ -130,8 +140,8 @@ class LocalExpertsGaussianProcess(Estimator):
 	@staticmethod
 	def _no_grad(xtest):
 		if torch.is_tensor(xtest) and xtest.requires_grad:
-			raise NotImplementedError("LocalExpertsGaussianProcess: input gradients of the combined posterior are not implemented (a follow-up); "
-									  "pass a test tensor without requires_grad")
+			raise NotImplementedError("LocalExpertsGaussianProcess: no autograd through the test tensor (requires_grad); the input gradients of the "
+									  "combined posterior are what mean_std_grad returns -- pass a test tensor without requires_grad")
 
 	def description(self):
 		return self.kernel_object.description() + "\nlambda=" + str(self.s) + "\nlocal experts (%s, expert_size %d, %d experts, partition %s)" % (
@@ -143,9 +153,6 @@ class LocalExpertsGaussianProcess(Estimator):
 		E = int(len(self._sizes))
 		npm = -(-int(self._sizes.max()) // 32) * 32 if E else 0
 		return {"E": E, "sizes": [int(v) for v in self._sizes], "launches": int(self.launches), "factor_bytes": 8 * E * npm * npm if self.fitted else 0}
-
-	def ucb_optimize(self, *args, **kwargs):
-		raise NotImplementedError("LocalExpertsGaussianProcess.ucb_optimize: needs input gradients of the combined posterior, which are not implemented")
 
 	def add_data_point(self, *args, **kwargs):
 		raise NotImplementedError("LocalExpertsGaussianProcess.add_data_point: appending to a fitted committee is not implemented; refit")
@@ -304,6 +311,127 @@ class LocalExpertsGaussianProcess(Estimator):
 	def ucb(self, xtest):
 		mu, s = self.mean_std(xtest)
 		return mu + 2 * s
+
+	# ------------------------------------------------------------------ input gradients
+	def _grad_chunks(self, m, d):
+		"""The gradient path's own rule: E * chunk * (2 + 2 d) output elements (mu_e, var_e and the two (E, chunk, d) gradient arrays) stay at or
+		below PREDICT_BUDGET; the launch's workspace is twice that of a prediction of the same chunk."""
+		E = max(len(self._sizes), 1)
+		step = max(1, min(self.max_size, PREDICT_BUDGET // (E * (2 + 2 * d))))
+		return [(a, min(a + step, m)) for a in range(0, m, step)]
+
+	@staticmethod
+	def _place(compact, D, cols):
+		"""Gradients over the selected coordinates (last dimension, in cols order) -> all D columns of the test points, zero where the kernel
+		term does not read: one device index_copy."""
+		if cols is None:
+			return compact
+		out = torch.zeros(tuple(compact.shape[:-1]) + (D,), dtype=compact.dtype, device=compact.device)
+		return out.index_copy_(compact.dim() - 1, cols.long(), compact)
+
+	def _experts_grad_device(self, xt):
+		"""(mu_e, var_e (E, M), gmu_e, gvar_e (E, M, d) over the selected coordinates): one stpy_experts_predict_grad launch per chunk."""
+		kind, kappa, cols, inv_ls, nmax = self._hyper
+		E, m, d = len(self._sizes), xt.shape[0], inv_ls.numel()
+		mu_e = torch.empty((E, m), dtype=torch.float64, device=xt.device)
+		var_e = torch.empty((E, m), dtype=torch.float64, device=xt.device)
+		gmu_e = torch.empty((E, m, d), dtype=torch.float64, device=xt.device)
+		gvar_e = torch.empty((E, m, d), dtype=torch.float64, device=xt.device)
+		for a, b in self._grad_chunks(m, d):
+			_lib.experts_predict_grad(kind, self._xs, self._offsets, nmax, inv_ls, kappa, self._factor, self._alpha, self._info, xt[a:b],
+									  mu_e[:, a:b], var_e[:, a:b], gmu_e[:, a:b], gvar_e[:, a:b], cols=cols)
+			self.launches += 1
+		return mu_e, var_e, gmu_e, gvar_e
+
+	def expert_mean_var_grad(self, xtest):
+		"""Every expert's posterior mean and latent VARIANCE at the test points, (E, M), and their input gradients, (E, M, D) with zeros in the
+		columns the kernel term does not read; placed like ``xtest`` (diagnostics)."""
+		self._no_grad(xtest)
+		if not self.fitted:
+			raise AttributeError("LocalExpertsGaussianProcess.expert_mean_var_grad needs a fitted object: call fit_gp first")
+		xt = _lib.to_device(xtest, torch.float64)
+		mu_e, var_e, gmu_e, gvar_e = self._experts_grad_device(xt)
+		cols = self._hyper[2]
+		return tuple(_lib.like_input(t, xtest) for t in (mu_e, var_e, self._place(gmu_e, xt.shape[1], cols), self._place(gvar_e, xt.shape[1], cols)))
+
+	def _mean_var_grad_device(self, xt):
+		"""(mu, var (M,), dmu, dstd (M, d) over the selected coordinates): per chunk one stpy_experts_predict_grad and one
+		stpy_experts_combine_grad launch.  mu and var carry the bits of ``_mean_var_device``."""
+		kind, kappa, cols, inv_ls, nmax = self._hyper
+		E, m, d = len(self._sizes), xt.shape[0], inv_ls.numel()
+		mu = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		var = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		dmu = torch.empty((m, d), dtype=torch.float64, device=xt.device)
+		dstd = torch.empty((m, d), dtype=torch.float64, device=xt.device)
+		chunks = self._grad_chunks(m, d)
+		work = _lib.experts_predict_grad_workspace(nmax, d, E, max(b - a for a, b in chunks), xt) if chunks else None
+		for a, b in chunks:
+			mu_e = torch.empty((E, b - a), dtype=torch.float64, device=xt.device)
+			var_e = torch.empty((E, b - a), dtype=torch.float64, device=xt.device)
+			gmu_e = torch.empty((E, b - a, d), dtype=torch.float64, device=xt.device)
+			gvar_e = torch.empty((E, b - a, d), dtype=torch.float64, device=xt.device)
+			_lib.experts_predict_grad(kind, self._xs, self._offsets, nmax, inv_ls, kappa, self._factor, self._alpha, self._info, xt[a:b],
+									  mu_e, var_e, gmu_e, gvar_e, cols=cols, work=work)
+			_lib.experts_combine_grad(COMBINE_MODES[self.combine], mu_e, var_e, gmu_e, gvar_e, kappa, mu[a:b], var[a:b], dmu[a:b], dstd[a:b])
+			self.launches += 2
+		return mu, var, dmu, dstd
+
+	def mean_std_grad(self, xtest):
+		"""Batched input gradients of the combined posterior: (d mu, d std), each (M, D), placed like ``xtest`` (GaussianProcess.mean_std_grad);
+		columns the kernel term does not read are zero.  The derivative of the function ``mean_std`` computes: through the combination rule, its
+		variance clamp (zero where it is active) and rBCM's variance-dependent weights.  Not fitted: zeros (the prior of a stationary kernel is
+		flat), without touching the device."""
+		xtest = torch.as_tensor(xtest).detach()
+		m = int(xtest.shape[0])
+		if not self.fitted:
+			dt = xtest.dtype if xtest.dtype in (torch.float32, torch.float64) else torch.float64
+			D = int(xtest.shape[1]) if xtest.dim() > 1 else int(self.d)
+			return torch.zeros((m, D), dtype=dt, device=xtest.device), torch.zeros((m, D), dtype=dt, device=xtest.device)
+		xt = _lib.to_device(xtest, torch.float64)
+		_, _, dmu, dstd = self._mean_var_grad_device(xt)
+		cols = self._hyper[2]
+		return _lib.like_input(self._place(dmu, xt.shape[1], cols), xtest), _lib.like_input(self._place(dstd, xt.shape[1], cols), xtest)
+
+	def ucb_optimize(self, beta, multistart=25, lcb=False):
+		"""GaussianProcess.ucb_optimize on the committee: maximise mu + sqrt(beta) sigma (mu - sqrt(beta) sigma with ``lcb``) over ``self.bounds``
+		from ``multistart`` uniform starts drawn with the reference's np.random calls in its order.  All starts are ONE stacked L-BFGS-B problem
+		(``_multistart_maximize`` of gauss_procc.py); every evaluation is one stpy_experts_predict_grad and one stpy_experts_combine_grad launch
+		per chunk of starts.  Returns (solution (d,), value) of the best start, never below the acquisition at any drawn start.
+		``self.optimize_info``: starts, start_values, evaluations, launches."""
+		from .gauss_procc import _draw_starts, _multistart_maximize
+		if not self.fitted:
+			raise NotImplementedError("LocalExpertsGaussianProcess.ucb_optimize: the object is not fitted, and the prior of a stationary kernel is "
+									  "flat: there is nothing to climb; call fit_gp first")
+		if self.bounds is None:
+			raise ValueError("ucb_optimize needs box bounds: set LocalExpertsGaussianProcess.bounds to a list of (low, high) per coordinate")
+		multistart = int(multistart)
+		if multistart < 1:
+			raise ValueError("LocalExpertsGaussianProcess.ucb_optimize: multistart=%d must be at least 1" % multistart)
+		bounds = tuple((float(a), float(b)) for (a, b) in self.bounds)
+		if len(bounds) != self.d:
+			raise ValueError("LocalExpertsGaussianProcess.ucb_optimize: %d bounds for d=%d" % (len(bounds), self.d))
+		starts = _draw_starts(multistart, self.d, bounds)
+		sign, sb = (-1.0 if lcb else 1.0), float(np.sqrt(beta))
+		cols, launches, first = self._hyper[2], self.launches, []
+
+		def evaluate(xt):
+			mu, var, dmu, dstd = self._mean_var_grad_device(xt)
+			val = mu + sign * sb * torch.sqrt(var)
+			if not first:
+				first.append(val.cpu().numpy())                    # the first evaluation is at the drawn starts
+			return val, self._place(dmu + sign * sb * dstd, xt.shape[1], cols)
+
+		def value(xt):          # (the final values need no gradients: the two launches of mean_std)
+			mu, var = self._mean_var_device(xt)
+			return mu + sign * sb * torch.sqrt(var)
+
+		sol, vals, evals = _multistart_maximize(evaluate, starts, bounds, self._xs.device, torch.float64, final=value)
+		x0, v0 = np.asarray(starts, dtype=np.float64), first[0]
+		keep = v0 > vals                                                   # the line search watches the SUM: a start its climb did not improve stays
+		sol[keep], vals[keep] = x0[keep], v0[keep]
+		index = int(np.argmax(vals))
+		self.optimize_info = {"starts": x0, "start_values": v0, "evaluations": evals, "launches": self.launches - launches}
+		return (torch.from_numpy(sol[index].copy()), torch.tensor(float(vals[index]), dtype=torch.float64))
 
 	# ------------------------------------------------------------------ the factorised evidence
 	def _check_overrides(self, kernel, X):

@@ -1,4 +1,4 @@
-// Local GP experts (stpy_experts_fit / _predict / _combine; LocalExpertsGaussianProcess): E exact GPs on E different blocks of the data under ONE
+// Local GP experts (stpy_experts_fit / _predict / _combine / _predict_grad / _combine_grad; LocalExpertsGaussianProcess): E exact GPs on E different blocks of the data under ONE
 // hyper-parameter candidate, the mirror image of the batched evidence (reduce.hip: B candidates on the same data), from the same one-workgroup
 // building blocks (lb_block.h).
 //
@@ -18,6 +18,10 @@
 // v o v straight from the accumulators: v is never stored.  The tile is 32 because that is the width of the panel product (two 16-column MFMA
 // halves share one A fragment); 64 columns would run the product twice over the same V for half as many k* slices, and the slice, 128 KB at
 // n_e = 512, is what bounds how many test points one launch can take.
+// With input gradients (stpy_experts_predict_grad / _combine_grad): the same grid and the same body for steps 1 - 3, v written out beside the sums,
+// w = K^-1 k* = V v by lb_panel<0> as it stands (A = V upper triangular from its row 0), then d mu / dx and d var / dx from direct differences,
+// one wave per test point; workspace two slices of 32 NPM doubles per (expert, tile).  The combination differentiates what it computes: the clamp
+// (zero where active) and rBCM's variance-dependent weights.
 // Every sum has a fixed order and no workgroup reads what another wrote: an expert's outputs are bit-identical wherever it sits in whatever batch.
 // Compiled inside api.hip (which includes this file, as it includes pchol.hip and the kmv family; it also compiles on its own, as the resource
 // test does) and NOT beside lml_batch_kernel in reduce.hip: more kernels in that translation unit change its LDS layout and with it its instructions.
@@ -43,6 +47,11 @@ struct ExpertsPredictArgs {
 	const double* xt; int64_t M, ldt; double* mu_e; double* var_e; int64_t ldm;
 	double* work; int64_t wslice; int ntiles;
 	int kind;
+};
+
+struct ExpertsPredictGradArgs {
+	ExpertsPredictArgs p;          // wslice: TWO halves of 32 NPM doubles
+	double* gmu_e; double* gvar_e; int64_t ldg, lde;          // (E, M, d): row stride ldg, expert stride lde
 };
 
 inline int64_t experts_npm(int64_t nmax) { return (nmax + 31) / 32 * 32; }
@@ -95,33 +104,19 @@ void experts_total_kernel(const double* value, const double* grad, int64_t ldg, 
 	}
 }
 
-__global__ __launch_bounds__(256, 2)
-void experts_predict_kernel(ExpertsPredictArgs p)
+// Steps 1 - 3 of a prediction for one (expert, tile): the ONE body of experts_predict_kernel and experts_predict_grad_kernel, so that the two write
+// the same bits to mu and var.  x, al, V: the expert's rows, its alpha and its factor slice; n of them, NP = n rounded up to 32; KT: 32 x NP doubles
+// of workspace.  With STORE_V the accumulators of step 3 are also written out, VT[t][k] = (L^-1 k*_t)_k for all 32 t and k < NP (zero for t >= mt and
+// k >= n): what the variance gradient's second triangular product reads.  As, Bs, ssq: the caller's LDS.  Entered and left by the whole workgroup.
+template <bool STORE_V>
+__device__ __forceinline__ void experts_predict_body(const ExpertsPredictArgs& p, const double* x, const double* al, const double* V, int n, int NP,
+                                                     int64_t t0, int mt, double* KT, double* VT, double* mu, double* var,
+                                                     double* As, double* Bs, double (*ssq)[EX_TILE])
 {
 	typedef Mfma<double>::v4 v4;
 	typedef Mfma<double>::v2 v2;
-	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
-	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
-	__shared__ double ssq[4][EX_TILE];
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-	const int e = blockIdx.x / p.ntiles, tile = blockIdx.x - e * p.ntiles;
-	const int64_t t0 = (int64_t)tile * EX_TILE;
-	const int mt = (int)min((int64_t)EX_TILE, p.M - t0);
-	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
-	double* mu = p.mu_e + (int64_t)e * p.ldm + t0;
-	double* var = p.var_e + (int64_t)e * p.ldm + t0;
-	if (p.info[e] != 0 || lo < 0 || hi < lo || hi > p.N || hi - lo > p.nmax) {          // (workgroup-uniform) an expert without a factor: the prior
-		if (tid < mt) {
-			mu[tid] = 0.0;
-			var[tid] = p.kappa;
-		}
-		return;
-	}
-	const int n = (int)(hi - lo), NP = (n + 31) & ~31, ld = NP;
-	const double* x = p.xs + lo * p.ldx;
-	const double* al = p.alpha + lo;
-	const double* V = p.factor + (int64_t)e * p.fslice;
-	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;          // KT[t][k] = k(xt_{t0 + t}, x_k), zero for t >= mt and k >= n
+	const int ld = NP;
 	const double* il = p.inv_ls;
 
 	// ---- 1. the k* tile
@@ -186,6 +181,13 @@ void experts_predict_kernel(ExpertsPredictArgs p)
 		for (int i = 0; i < 4; ++i) {
 			q0 = fma(acc0[i], acc0[i], q0);
 			q1 = fma(acc1[i], acc1[i], q1);
+			if (STORE_V) {
+				const int row = r0 + 16 * w + Mfma<double>::crow(lane, i);
+				if (row < NP) {
+					VT[(int64_t)fr * ld + row] = acc0[i];
+					VT[(int64_t)(16 + fr) * ld + row] = acc1[i];
+				}
+			}
 		}
 	}
 	// (lanes fr, fr + 16, fr + 32, fr + 48 hold the four row groups of column fr: a symmetric tree, then the four waves in index order)
@@ -199,6 +201,156 @@ void experts_predict_kernel(ExpertsPredictArgs p)
 	if (tid < mt) var[tid] = p.kappa - (((ssq[0][tid] + ssq[1][tid]) + ssq[2][tid]) + ssq[3][tid]);
 }
 
+// whether expert e has a factor the launch is sized for (workgroup-uniform)
+__device__ __forceinline__ bool experts_has_factor(const ExpertsPredictArgs& p, int e, int64_t lo, int64_t hi)
+{
+	return p.info[e] == 0 && lo >= 0 && hi >= lo && hi <= p.N && hi - lo <= p.nmax;
+}
+
+__global__ __launch_bounds__(256, 2)
+void experts_predict_kernel(ExpertsPredictArgs p)
+{
+	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
+	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
+	__shared__ double ssq[4][EX_TILE];
+	const int tid = threadIdx.x;
+	const int e = blockIdx.x / p.ntiles, tile = blockIdx.x - e * p.ntiles;
+	const int64_t t0 = (int64_t)tile * EX_TILE;
+	const int mt = (int)min((int64_t)EX_TILE, p.M - t0);
+	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
+	double* mu = p.mu_e + (int64_t)e * p.ldm + t0;
+	double* var = p.var_e + (int64_t)e * p.ldm + t0;
+	if (!experts_has_factor(p, e, lo, hi)) {          // (workgroup-uniform) an expert without a factor: the prior
+		if (tid < mt) {
+			mu[tid] = 0.0;
+			var[tid] = p.kappa;
+		}
+		return;
+	}
+	const int n = (int)(hi - lo), NP = (n + 31) & ~31;
+	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;          // KT[t][k] = k(xt_{t0 + t}, x_k), zero for t >= mt and k >= n
+	experts_predict_body<false>(p, p.xs + lo * p.ldx, p.alpha + lo, p.factor + (int64_t)e * p.fslice, n, NP, t0, mt, KT, nullptr, mu, var, As, Bs, ssq);
+}
+
+// The prediction with its input gradients, per (expert, tile of 32 test points); the workspace slice is two halves of 32 NPM doubles.
+//   1 - 3. experts_predict_body<true>: mu, var as experts_predict_kernel writes them, and v = L^-1 k* kept: VT[t][k] (second half of the slice);
+//   4. w = K^-1 k* = L^-T v = V v, W[i][t] = sum_{k >= i} V[i][k] VT[t][k]: lb_panel<0> with A = V upper triangular from its row 0 (the round that
+//      starts at row r0 reads V from column r0 on; the block just below the block diagonal is stored as zero, what lies further below is not
+//      read), B = VT, C = W (NP x 32, row stride 32) over the k* tile, which is dead by then;
+//   5. with F = lb_dfactor(r^2), r^2 recomputed from the points (direct differences), per selected column m:
+//        gmu[t][m]  = -kappa il_m^2 sum_k alpha_k F_tk (xt_m - x_km),     gvar[t][m] = 2 kappa il_m^2 sum_k w_tk F_tk (xt_m - x_km)
+//      (d k(x, x) / dx = 0 for a stationary term; Matern 1/2 on a coincident pair: F = 0): one wave per test point, lanes strided over k, a fixed
+//      shuffle tree, four columns per pass over k; the first pass leaves F in VT[t][k] (dead after step 4; each lane re-reads what it stored).
+__global__ __launch_bounds__(256, 2)
+void experts_predict_grad_kernel(ExpertsPredictGradArgs g)
+{
+	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
+	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
+	__shared__ double ssq[4][EX_TILE];
+	const ExpertsPredictArgs& p = g.p;
+	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+	const int e = blockIdx.x / p.ntiles, tile = blockIdx.x - e * p.ntiles;
+	const int64_t t0 = (int64_t)tile * EX_TILE;
+	const int mt = (int)min((int64_t)EX_TILE, p.M - t0);
+	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
+	double* mu = p.mu_e + (int64_t)e * p.ldm + t0;
+	double* var = p.var_e + (int64_t)e * p.ldm + t0;
+	double* gmu = g.gmu_e + (int64_t)e * g.lde + t0 * g.ldg;
+	double* gvar = g.gvar_e + (int64_t)e * g.lde + t0 * g.ldg;
+	if (!experts_has_factor(p, e, lo, hi)) {          // (workgroup-uniform) an expert without a factor: the prior, which is flat
+		if (tid < mt) {
+			mu[tid] = 0.0;
+			var[tid] = p.kappa;
+		}
+		for (int i = tid; i < mt * p.d; i += 256) {
+			const int t = i / p.d, m = i - t * p.d;
+			gmu[(int64_t)t * g.ldg + m] = 0.0;
+			gvar[(int64_t)t * g.ldg + m] = 0.0;
+		}
+		return;
+	}
+	const int n = (int)(hi - lo), NP = (n + 31) & ~31;
+	const double* x = p.xs + lo * p.ldx;
+	const double* al = p.alpha + lo;
+	const double* V = p.factor + (int64_t)e * p.fslice;
+	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;          // the k* tile, then W[k][t] = (K^-1 k*_t)_k
+	double* VT = KT + (p.wslice >> 1);                             // VT[t][k] = (L^-1 k*_t)_k, then F_tk
+	experts_predict_body<true>(p, x, al, V, n, NP, t0, mt, KT, VT, mu, var, As, Bs, ssq);
+
+	// ---- 4. W = V VT^T (lb_panel opens with a barrier: the stores of VT, and the last reads of the k* tile, are behind it)
+	lb_panel<0>(KT, EX_TILE, V, NP, VT, NP, NP, NP, 0, As, Bs);
+	__syncthreads();
+
+	// ---- 5. the gradients
+	const double* il = p.inv_ls;
+	for (int t = w; t < mt; t += 4) {
+		const double* xt = p.xt + (t0 + t) * p.ldt;
+		double* Ft = VT + (int64_t)t * NP;
+		for (int m0 = 0; m0 < p.d; m0 += 4) {
+			double sm[4] = {0.0, 0.0, 0.0, 0.0}, sv[4] = {0.0, 0.0, 0.0, 0.0};
+			for (int k = lane; k < n; k += 64) {
+				const double* xk = x + (int64_t)k * p.ldx;
+				double F;
+				if (m0 == 0) {
+					F = lb_dfactor(p.kind, lb_r2(xk, xt, p.cols, il, p.d));
+					Ft[k] = F;
+				} else
+					F = Ft[k];
+				const double a = al[k] * F, b = KT[(int64_t)k * EX_TILE + t] * F;
+#pragma unroll
+				for (int c = 0; c < 4; ++c)
+					if (m0 + c < p.d) {
+						const int col = p.cols ? p.cols[m0 + c] : m0 + c;
+						const double u = xt[col] - xk[col];
+						sm[c] = fma(a, u, sm[c]);
+						sv[c] = fma(b, u, sv[c]);
+					}
+			}
+#pragma unroll
+			for (int c = 0; c < 4; ++c) {
+#pragma unroll
+				for (int o = 32; o > 0; o >>= 1) {
+					sm[c] += __shfl_xor(sm[c], o);
+					sv[c] += __shfl_xor(sv[c], o);
+				}
+			}
+			if (lane == 0) {
+#pragma unroll
+				for (int c = 0; c < 4; ++c)
+					if (m0 + c < p.d) {
+						const double s2 = p.kappa * (il[m0 + c] * il[m0 + c]);
+						gmu[(int64_t)t * g.ldg + m0 + c] = -(s2 * sm[c]);
+						gvar[(int64_t)t * g.ldg + m0 + c] = 2.0 * (s2 * sv[c]);
+					}
+			}
+		}
+	}
+}
+
+// One expert's term of the combination, the step both experts_combine_kernel and experts_combine_grad_kernel take (the same bits in mu and var):
+// v = clamp(var_e), c = 1 / v, beta by the mode, and the three running sums in expert order.
+struct ExpertsCombineSums { double prec, wm, bsum; };
+
+__device__ __forceinline__ void experts_combine_step(int mode, double ve, double me, double vmin, double kappa, double logk, double inv_e,
+                                                     double& v, double& c, double& beta, ExpertsCombineSums& s)
+{
+	v = fmin(fmax(ve, vmin), kappa);
+	c = 1.0 / v;
+	beta = mode == 1 ? inv_e : (mode == 3 ? 0.5 * (logk - log(v)) : 1.0);
+	s.prec = fma(beta, c, s.prec);
+	s.wm = fma(beta * c, me, s.wm);
+	s.bsum += beta;
+}
+
+// 1 / var from the sums
+__device__ __forceinline__ double experts_combine_prec(int mode, int64_t E, double kappa, const ExpertsCombineSums& s)
+{
+	double prec = s.prec;
+	if (mode == 2) prec += (1.0 - (double)E) / kappa;
+	if (mode == 3) prec += (1.0 - s.bsum) / kappa;
+	return prec;
+}
+
 // one thread per test point, experts in expert order (the table of stpy_experts_combine in the header)
 __global__ __launch_bounds__(256)
 void experts_combine_kernel(int mode, int64_t E, int64_t M, const double* mu_e, const double* var_e, int64_t ldm, double kappa, double* mu, double* var)
@@ -206,20 +358,76 @@ void experts_combine_kernel(int mode, int64_t E, int64_t M, const double* mu_e, 
 	const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
 	if (t >= M) return;
 	const double vmin = kappa * 2.220446049250313e-16, logk = log(kappa), inv_e = 1.0 / (double)E;
-	double prec = 0.0, wm = 0.0, bsum = 0.0;
+	ExpertsCombineSums s{0.0, 0.0, 0.0};
 	for (int64_t e = 0; e < E; ++e) {
-		const double v = fmin(fmax(var_e[e * ldm + t], vmin), kappa);
-		const double c = 1.0 / v;
-		const double beta = mode == 1 ? inv_e : (mode == 3 ? 0.5 * (logk - log(v)) : 1.0);
-		prec = fma(beta, c, prec);
-		wm = fma(beta * c, mu_e[e * ldm + t], wm);
-		bsum += beta;
+		double v, c, beta;
+		experts_combine_step(mode, var_e[e * ldm + t], mu_e[e * ldm + t], vmin, kappa, logk, inv_e, v, c, beta, s);
 	}
-	if (mode == 2) prec += (1.0 - (double)E) / kappa;
-	if (mode == 3) prec += (1.0 - bsum) / kappa;
-	const double vout = 1.0 / prec;
+	const double vout = 1.0 / experts_combine_prec(mode, E, kappa, s);
 	var[t] = vout;
-	mu[t] = vout * wm;
+	mu[t] = vout * s.wm;
+}
+
+struct ExpertsCombineGradArgs {
+	int mode, d; int64_t E, M; const double* mu_e; const double* var_e; int64_t ldm; const double* gmu_e; const double* gvar_e; int64_t ldg, lde;
+	double kappa; double* mu; double* var; double* dmu; double* dstd; int64_t ldo;
+};
+
+// The combination and its chain rule (the table of stpy_experts_combine_grad in the header): one thread per test point, experts in expert order,
+// EXC_COLS coordinates per pass over the experts; the first pass is also the forward pass (a thread walks E experts one after the other, and
+// what a pass costs is the latency of that walk, so the passes are what there is to save: one for d <= 8).  v = clamp(var_e): dv = gvar_e where
+// kappa eps <= var_e <= kappa (the clamp is inactive, ties included), else 0 -- the derivative of the function as implemented.
+constexpr int EXC_COLS = 8;
+
+__global__ __launch_bounds__(256)
+void experts_combine_grad_kernel(ExpertsCombineGradArgs p)
+{
+	const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (t >= p.M) return;
+	const int mode = p.mode;
+	const double kappa = p.kappa;
+	const double vmin = kappa * 2.220446049250313e-16, logk = log(kappa), inv_e = 1.0 / (double)p.E;
+	double vout = 0.0, wm = 0.0, half_isd = 0.0;
+	for (int m0 = 0; m0 < p.d; m0 += EXC_COLS) {
+		ExpertsCombineSums s{0.0, 0.0, 0.0};
+		double dprec[EXC_COLS], dwm[EXC_COLS], dbs[EXC_COLS];
+#pragma unroll
+		for (int q = 0; q < EXC_COLS; ++q) dprec[q] = dwm[q] = dbs[q] = 0.0;
+		for (int64_t e = 0; e < p.E; ++e) {
+			const double ve = p.var_e[e * p.ldm + t], me = p.mu_e[e * p.ldm + t];
+			double v, c, beta;
+			experts_combine_step(mode, ve, me, vmin, kappa, logk, inv_e, v, c, beta, s);
+			const bool open = ve >= vmin && ve <= kappa;
+			const double bc = beta * c, cc = -(c * c), hv = -0.5 * c;          // (d c = cc dv, d beta = hv dv under rBCM)
+			const double* gm = p.gmu_e + e * p.lde + t * p.ldg + m0;
+			const double* gv = p.gvar_e + e * p.lde + t * p.ldg + m0;
+#pragma unroll
+			for (int q = 0; q < EXC_COLS; ++q)
+				if (m0 + q < p.d) {
+					const double dv = open ? gv[q] : 0.0;
+					const double dbeta = mode == 3 ? hv * dv : 0.0;
+					const double dbc = fma(dbeta, c, beta * (cc * dv));          // d (beta c)
+					dprec[q] += dbc;
+					dwm[q] += fma(dbc, me, bc * gm[q]);
+					dbs[q] += dbeta;
+				}
+		}
+		if (m0 == 0) {          // (every pass recomputes the same sums; the first one stores them)
+			vout = 1.0 / experts_combine_prec(mode, p.E, kappa, s);
+			wm = s.wm;
+			half_isd = 0.5 / sqrt(vout);
+			p.var[t] = vout;
+			p.mu[t] = vout * wm;
+		}
+#pragma unroll
+		for (int q = 0; q < EXC_COLS; ++q)
+			if (m0 + q < p.d) {
+				const double dp = mode == 3 ? dprec[q] - dbs[q] / kappa : dprec[q];
+				const double dvar = -(vout * vout) * dp;
+				p.dmu[t * p.ldo + m0 + q] = fma(dvar, wm, vout * dwm[q]);
+				p.dstd[t * p.ldo + m0 + q] = dvar * half_isd;
+			}
+	}
 }
 
 }  // namespace stpy
@@ -346,6 +554,78 @@ int stpy_experts_combine(int mode, int64_t E, int64_t M, const void* mu_e, const
 	hipLaunchKernelGGL(experts_combine_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mode, E, M, (const double*)mu_e,
 	                   (const double*)var_e, ldm, kappa, (double*)mu, (double*)var);
 	return check_launch("experts_combine");
+}
+
+int64_t stpy_experts_predict_grad_workspace_bytes(int dtype, int64_t nmax, int d, int64_t E, int64_t M)
+{
+	return 2 * stpy_experts_predict_workspace_bytes(dtype, nmax, d, E, M);
+}
+
+int stpy_experts_predict_grad(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const int32_t* offsets,
+                              int64_t E, int64_t nmax, const void* inv_ls, double kappa, const void* factor, int64_t factor_bytes,
+                              const void* alpha, const int32_t* info, const void* xt, int64_t M, int64_t ldt,
+                              void* mu_e, void* var_e, int64_t ldm, void* gmu_e, void* gvar_e, int64_t ldg, int64_t lde,
+                              void* work, int64_t work_bytes, void* stream)
+{
+	const char* who = "stpy_experts_predict_grad";
+	if (E == 0 || N == 0 || M == 0) return 0;
+	int rc;
+	if (experts_common_refused(who, kind, dtype, N, ldx, d, E, nmax, &rc)) return rc;
+	const int64_t ntiles = M < 0 ? 0 : (M + EX_TILE - 1) / EX_TILE;
+	if (M < 0 || E * ntiles > INT32_MAX) { set_error("%s: M=%lld out of range (E x tiles of 32 test points must stay below 2^31)", who, (long long)M); return -9; }
+	if (ldt < d || ldm < M) { set_error("%s: leading dimensions ldt=%lld (d=%d) ldm=%lld (M=%lld)", who, (long long)ldt, d, (long long)ldm, (long long)M); return ldt < d ? -5 : -13; }
+	if (ldg < d || lde / ldg < M) {          // (lde < M ldg without forming the product)
+		set_error("%s: gradient strides ldg=%lld (d=%d) lde=%lld (at least M ldg, M=%lld)", who, (long long)ldg, d, (long long)lde, (long long)M);
+		return -19;
+	}
+	if (!xs || !offsets || !inv_ls || !factor || !alpha || !info || !xt || !mu_e || !var_e || !gmu_e || !gvar_e || !work) { set_error("%s: null pointer", who); return -3; }
+	if (!(kappa > 0.0) || !is_finite(kappa)) { set_error("%s: kappa=%g must be positive and finite", who, kappa); return -11; }
+	const int64_t need = stpy_experts_predict_grad_workspace_bytes(dtype, nmax, d, E, M), fneed = stpy_experts_factor_bytes(dtype, nmax, E);
+	if (work_bytes < need) {
+		set_error("%s: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", who, (long long)work_bytes, (long long)need);
+		return -20;
+	}
+	if (factor_bytes < fneed) {
+		set_error("%s: factor buffer of %lld bytes, %lld needed (stpy_experts_factor_bytes)", who, (long long)factor_bytes, (long long)fneed);
+		return -22;
+	}
+	if ((((uintptr_t)xs | (uintptr_t)xt | (uintptr_t)alpha | (uintptr_t)mu_e | (uintptr_t)var_e | (uintptr_t)gmu_e | (uintptr_t)gvar_e) & 7)
+	    || (((uintptr_t)work | (uintptr_t)factor) & 15)) {
+		set_error("%s: work and factor must be 16-byte aligned, the other arrays 8-byte", who);
+		return -21;
+	}
+	ExpertsPredictGradArgs g{{(const double*)xs, N, ldx, d, cols, offsets, (int)nmax, (const double*)inv_ls, kappa, (const double*)factor, experts_factor_slice(nmax),
+	                          (const double*)alpha, info, (const double*)xt, M, ldt, (double*)mu_e, (double*)var_e, ldm, (double*)work, 2 * experts_predict_slice(nmax),
+	                          (int)ntiles, kind},
+	                         (double*)gmu_e, (double*)gvar_e, ldg, lde};
+	hipLaunchKernelGGL(experts_predict_grad_kernel, dim3((unsigned)(E * ntiles)), dim3(256), 0, (hipStream_t)stream, g);
+	return check_launch("experts_predict_grad");
+}
+
+int stpy_experts_combine_grad(int mode, int64_t E, int64_t M, int d, const void* mu_e, const void* var_e, int64_t ldm,
+                              const void* gmu_e, const void* gvar_e, int64_t ldg, int64_t lde, double kappa,
+                              void* mu, void* var, void* dmu, void* dstd, int64_t ldo, void* stream)
+{
+	const char* who = "stpy_experts_combine_grad";
+	if (E == 0 || M == 0) return 0;
+	if (mode < 0 || mode > 3) { set_error("%s: mode %d (0 PoE, 1 gPoE, 2 BCM, 3 rBCM)", who, mode); return -10; }
+	if (E < 0 || M < 0 || M > (int64_t)INT32_MAX * 256) { set_error("%s: E=%lld M=%lld out of range", who, (long long)E, (long long)M); return -9; }
+	if (d < 1) { set_error("%s: bad dimension d=%d", who, d); return -6; }
+	if (ldm < M) { set_error("%s: leading dimension ldm=%lld (M=%lld)", who, (long long)ldm, (long long)M); return -13; }
+	if (ldg < d || lde / ldg < M || ldo < d) {
+		set_error("%s: gradient strides ldg=%lld ldo=%lld (d=%d) lde=%lld (at least M ldg, M=%lld)", who, (long long)ldg, (long long)ldo, d, (long long)lde, (long long)M);
+		return -19;
+	}
+	if (!mu_e || !var_e || !gmu_e || !gvar_e || !mu || !var || !dmu || !dstd) { set_error("%s: null pointer", who); return -3; }
+	if (!(kappa > 0.0) || !is_finite(kappa)) { set_error("%s: kappa=%g must be positive and finite", who, kappa); return -11; }
+	if (((uintptr_t)mu_e | (uintptr_t)var_e | (uintptr_t)gmu_e | (uintptr_t)gvar_e | (uintptr_t)mu | (uintptr_t)var | (uintptr_t)dmu | (uintptr_t)dstd) & 7) {
+		set_error("%s: arrays must be 8-byte aligned", who);
+		return -21;
+	}
+	ExpertsCombineGradArgs p{mode, d, E, M, (const double*)mu_e, (const double*)var_e, ldm, (const double*)gmu_e, (const double*)gvar_e, ldg, lde, kappa,
+	                         (double*)mu, (double*)var, (double*)dmu, (double*)dstd, ldo};
+	hipLaunchKernelGGL(experts_combine_grad_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+	return check_launch("experts_combine_grad");
 }
 
 }  // extern "C"

@@ -8,11 +8,14 @@ Local experts: what a fit, an evidence gradient and a prediction cost (DESIGN.md
               stpy_experts_predict + stpy_experts_combine at M = 4096
   end to end  LocalExpertsGaussianProcess at N = 1 048 576, d = 8, expert_size = 256: fit_gp, one log_marginal with its gradient, mean_std of
               4096 points; workspace and factor bytes at that size
+  gradients   on that committee: stpy_experts_predict_grad + stpy_experts_combine_grad beside stpy_experts_predict + stpy_experts_combine on the
+              same chunks of test points at M = 256 and M = 4096 (device events, the ratio per round), mean_std_grad beside mean_std (host
+              clocks; the gradient path has its own, smaller chunks), and one ucb_optimize(multistart=256) with its evaluation count
 
 Kernel times are device events around `--reps` back-to-back launches after a warm-up, median and spread over `--rounds` rounds; end-to-end times
 are host clocks around calls that end in a read-back or a synchronise.  Prints one JSON line.
 
-usage: python tools/experts_bench.py [--reps 5] [--rounds 5] [--parent-lib PATH]... [--n 256] [--d 8] [--kernels-only] [--quick]
+usage: python tools/experts_bench.py [--reps 5] [--rounds 5] [--parent-lib PATH]... [--n 256] [--d 8] [--kernels-only] [--no-grad] [--quick]
 """
 import argparse
 import ctypes
@@ -91,6 +94,7 @@ def main():
 	ap.add_argument("--d", type=int, default=8)
 	ap.add_argument("--kernels-only", action="store_true")
 	ap.add_argument("--quick", action="store_true")
+	ap.add_argument("--no-grad", action="store_true", help="skip the input-gradient section (prediction with and without gradients, ucb_optimize)")
 	a = ap.parse_args()
 	if not torch.cuda.is_available():
 		print(json.dumps({"tool": "experts_bench", "error": "no GPU: nothing measured"}))
@@ -193,6 +197,62 @@ def main():
 	out["end_to_end"] = dict({k: _stats(v) for k, v in e2e.items()}, N=N, E=Ebig, M=M, evidence=float(f.detach()), dgamma=float(g.grad), predict_chunk=gp._chunks(M)[0][1],
 							 factor_bytes=gp.experts_info["factor_bytes"], fit_workspace_bytes=int(lib.stpy_experts_fit_workspace_bytes(0, n_e, d, Ebig)),
 							 predict_workspace_bytes=int(lib.stpy_experts_predict_workspace_bytes(0, n_e, d, Ebig, gp._chunks(M)[0][1])))
+	if a.no_grad:
+		print(json.dumps(out))
+		return 0
+
+	# ---- input gradients on the fitted committee: stpy_experts_predict_grad + _combine_grad beside stpy_experts_predict + _combine on the SAME chunks
+	# (the prediction's), device events; then the class (its own chunk rule for the gradient path), host clocks; then one ucb_optimize
+	kind, kappa, cols, il, nmax = gp._hyper
+	out["gradients"] = {}
+	for Mk in sorted({min(256, M), M}):
+		xk = xtd[:Mk]
+		chunks = gp._chunks(Mk)
+		cm = max(b - c for c, b in chunks)
+		z = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)
+		mu_e, var_e, gmu_e, gvar_e = z(Ebig, cm), z(Ebig, cm), z(Ebig, cm, d), z(Ebig, cm, d)
+		mu, var, dmu, dstd = z(Mk), z(Mk), z(Mk, d), z(Mk, d)
+		pw = _lib._work(lib.stpy_experts_predict_workspace_bytes(0, nmax, d, Ebig, cm), xd)
+		gw = _lib.experts_predict_grad_workspace(nmax, d, Ebig, cm, xd)
+
+		def plain():
+			for c, b in chunks:
+				_lib.experts_predict(kind, gp._xs, gp._offsets, nmax, il, kappa, gp._factor, gp._alpha, gp._info, xk[c:b], mu_e[:, :b - c], var_e[:, :b - c], cols=cols, work=pw)
+				_lib.experts_combine(3, mu_e[:, :b - c], var_e[:, :b - c], kappa, mu[c:b], var[c:b])
+
+		def grad():
+			for c, b in chunks:
+				_lib.experts_predict_grad(kind, gp._xs, gp._offsets, nmax, il, kappa, gp._factor, gp._alpha, gp._info, xk[c:b], mu_e[:, :b - c], var_e[:, :b - c],
+										  gmu_e[:, :b - c], gvar_e[:, :b - c], cols=cols, work=gw)
+				_lib.experts_combine_grad(3, mu_e[:, :b - c], var_e[:, :b - c], gmu_e[:, :b - c], gvar_e[:, :b - c], kappa, mu[c:b], var[c:b], dmu[c:b], dstd[c:b])
+		tk = {"predict_combine": [], "predict_grad_combine_grad": [], "mean_std": [], "mean_std_grad": []}
+		plain(), grad(), gp.mean_std(xk), gp.mean_std_grad(xk)          # warm-up
+		torch.cuda.synchronize()
+		for r in range(max(a.rounds, 1)):
+			tk["predict_combine"].append(_events(plain, a.reps))
+			tk["predict_grad_combine_grad"].append(_events(grad, a.reps))
+			for name, fn in (("mean_std", gp.mean_std), ("mean_std_grad", gp.mean_std_grad)):
+				torch.cuda.synchronize()
+				t0 = time.perf_counter()
+				fn(xk)
+				torch.cuda.synchronize()
+				tk[name].append((time.perf_counter() - t0) * 1e3)
+		ratio = [g_ / p_ for g_, p_ in zip(tk["predict_grad_combine_grad"], tk["predict_combine"])]
+		out["gradients"]["M=%d" % Mk] = dict({k: _stats(v) for k, v in tk.items()}, chunk=cm, grad_chunk=gp._grad_chunks(Mk, d)[0][1],
+											 grad_over_plain_median=float(np.median(ratio)), grad_over_plain_min=min(ratio), grad_over_plain_max=max(ratio),
+											 grad_workspace_bytes=gw.numel(), plain_workspace_bytes=pw.numel())
+		del mu_e, var_e, gmu_e, gvar_e, pw, gw
+		torch.cuda.empty_cache()
+	print(json.dumps({"gradients_so_far": out["gradients"]}), file=sys.stderr, flush=True)
+	gp.bounds = [(0.0, 1.0)] * d
+	np.random.seed(0)
+	starts = 16 if a.quick else 256
+	torch.cuda.synchronize()
+	t0 = time.perf_counter()
+	sol, val = gp.ucb_optimize(4.0, multistart=starts)
+	torch.cuda.synchronize()
+	out["ucb_optimize"] = {"multistart": starts, "ms": (time.perf_counter() - t0) * 1e3, "evaluations": gp.optimize_info["evaluations"],
+						   "launches": gp.optimize_info["launches"], "value": float(val), "best_start_value": float(gp.optimize_info["start_values"].max())}
 	print(json.dumps(out))
 	return 0
 
