@@ -479,6 +479,63 @@ int stpy_experts_combine_grad(int mode, int64_t E, int64_t M, int d, const void*
                               void* mu, void* var, void* dmu, void* dstd, int64_t ldo, void* stream);
 
 /*
+ * Local GP experts, routed prediction: every test point asks only its k nearest experts, nearest by the distance to the experts' centroids in
+ * scaled coordinates.  The (expert, point) pairs of a prediction drop from E M to k M, whatever N is.  xs, offsets, cols, inv_ls, kappa, factor,
+ * alpha, info, xt as for stpy_experts_predict; float64 only.
+ *
+ * stpy_experts_centroids: one wave per expert,
+ *   cent[e*ldc + m]    = (sum over the expert's rows, in row order, of xs[i*ldx + cols[m]] * inv_ls[m]) / n_e,   m < d, ldc >= d
+ * An expert without rows, or whose offsets leave [0, N] or decrease, gets +inf in every coordinate: it is never nearer than an expert with rows.
+ * stpy_experts_route: one wave per test point.  D_e = sum_m (xt[t*ldt + cols[m]] * inv_ls[m] - cent[e*ldc + m])^2, m ascending, capped at
+ * DBL_MAX (a NaN counts as DBL_MAX); D_e = +inf where cent[e*ldc] is +inf.  The k experts with the smallest D_e are selected, ties going to the
+ * lower expert id (so experts without rows come last, by id), and written ASCENDING IN EXPERT ID:
+ *   sel[t*k + j]       int32, j < k, sel[t*k] < sel[t*k + 1] < ...
+ * so that a combination over the k slots keeps the experts' order.  1 <= k <= min(E, stpy_experts_route_max_k()); the cap is 16: a lane of the
+ * routing kernel holds its candidates as a sorted list in registers.  E is not bounded by the kernel (lanes stride over the experts).
+ * stpy_experts_predict_routed / _predict_routed_grad: stpy_experts_predict / _predict_grad on a WORK LIST of T tiles in place of the grid of
+ * E x ceil(M / 32) tiles.  Tile w belongs to expert wexp[w] (device int32[T]) and its column c to pair wpair[32 w + c] = t*k + j (device
+ * int32[32 T]): test point t < M, slot j < k of its selection.  wexp[w] outside [0, E): the tile is unused; a pair id outside [0, M k), -1 by
+ * convention: the column is empty.  Whatever the two arrays hold, nothing is written out of bounds; a pair listed twice is computed twice, with
+ * the same bits.  The caller builds the list from sel on the device (a stable sort of the pair ids by expert, counts, running sums of
+ * ceil(count / 32), a scatter); T = floor(M k / 32) + min(E, M k) tiles always suffice.  The results of pair (t, j) go to slot j of point t:
+ *   mu_s[j*ldm + t], var_s[j*ldm + t]                         (k x ldm, ldm >= M)
+ *   gmu_s[j*lde + t*ldg + m], gvar_s[j*lde + t*ldg + m]       (k x M x d, ldg >= d, lde >= M*ldg)
+ * exactly the layout stpy_experts_combine / _combine_grad read with E := k, so those two are the combination of a routed prediction as they
+ * stand -- with the consequence that gPoE's beta is 1 / k and BCM's correction (1 - k) / kappa.  Slots of pairs the list does not hold are not
+ * written.  An expert with info[e] != 0, without rows or mis-sized puts the prior into its slots (mu 0, var kappa, zero gradients).
+ * Bit contract: the four kernels run ONE body, every sum of which runs over an expert's rows for one fixed test point: the entries at (j, t)
+ * carry the bits stpy_experts_predict / _predict_grad write at (sel[t*k + j], t); with k = E the routed prediction is the unrouted one.
+ * `work`: 32 NPM doubles per tile (T * 32 * NPM in all), twice that with gradients; the queries take T.
+ * The gradients are those of the function computed WITH THE SELECTION HELD FIXED: the routed posterior is piecewise smooth and jumps where the
+ * k-th and the (k + 1)-th nearest expert of a point swap.
+ * No atomics, fixed summation orders: two calls are bit-identical.  Refused before any HIP call, with the codes of the block above, plus: k
+ * outside [1, min(E, cap)] (-23); M k or T at or above 2^31 (-9); ldc < d (-5).  E == 0, M == 0, T == 0 (or N == 0 for the predictions):
+ * returns 0, nothing is read or written.
+ */
+int64_t stpy_experts_route_max_k(void);
+int stpy_experts_centroids(int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const int32_t* offsets, int64_t E,
+                           const void* inv_ls, void* cent, int64_t ldc, void* stream);
+int stpy_experts_route(int dtype, const void* cent, int64_t ldc, int64_t E, int d, const int32_t* cols, const void* inv_ls,
+                       const void* xt, int64_t M, int64_t ldt, int k, int32_t* sel, void* stream);
+int64_t stpy_experts_predict_routed_workspace_bytes(int dtype, int64_t nmax, int d, int64_t T);
+int stpy_experts_predict_routed(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols,
+                                const int32_t* offsets, int64_t E, int64_t nmax, const void* inv_ls, double kappa,
+                                const void* factor, int64_t factor_bytes, const void* alpha, const int32_t* info,
+                                const void* xt, int64_t M, int64_t ldt,
+                                int k, const int32_t* wexp, const int32_t* wpair, int64_t T,
+                                void* mu_s, void* var_s, int64_t ldm,
+                                void* work, int64_t work_bytes, void* stream);
+int64_t stpy_experts_predict_routed_grad_workspace_bytes(int dtype, int64_t nmax, int d, int64_t T);
+int stpy_experts_predict_routed_grad(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols,
+                                     const int32_t* offsets, int64_t E, int64_t nmax, const void* inv_ls, double kappa,
+                                     const void* factor, int64_t factor_bytes, const void* alpha, const int32_t* info,
+                                     const void* xt, int64_t M, int64_t ldt,
+                                     int k, const int32_t* wexp, const int32_t* wpair, int64_t T,
+                                     void* mu_s, void* var_s, int64_t ldm,
+                                     void* gmu_s, void* gvar_s, int64_t ldg, int64_t lde,
+                                     void* work, int64_t work_bytes, void* stream);
+
+/*
  * Greedy pivoted partial Cholesky of the kernel matrix K_il = kappa phi(|(x_i - x_l)[cols] o inv_ls|), columns generated on the fly: the landmark
  * choice of NystromFeatures(approx="pivoted") (the reference's nystrom_fea.py has uniform / leverage sampling only).  K is never formed:
  * O(n m) memory, O(n m^2) work.  kind, cols, inv_ls, kappa as for stpy_gram; SE and MATERN12 / 32 / 52 only.  Kernel values come from direct

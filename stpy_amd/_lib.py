@@ -81,6 +81,15 @@ SIGNATURES = {
 	"stpy_experts_predict_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64,
 								  _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
 	"stpy_experts_combine_grad": (_i32, [_i32, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _dbl, _vp, _vp, _vp, _vp, _i64, _vp]),
+	"stpy_experts_route_max_k": (_i64, []),
+	"stpy_experts_centroids": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+	"stpy_experts_route": (_i32, [_i32, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp]),
+	"stpy_experts_predict_routed_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
+	"stpy_experts_predict_routed": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
+										_i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
+	"stpy_experts_predict_routed_grad_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
+	"stpy_experts_predict_routed_grad": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _dbl, _vp, _i64, _vp, _vp, _vp, _i64, _i64,
+											 _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
 	"stpy_pchol_workspace_bytes": (_i64, [_i32, _i64, _i32, _i64]),
 	"stpy_pchol": (_i32, [_i32, _i32, _vp, _i64, _i64, _i32, _vp, _vp, _dbl, _i64, _dbl, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
 	"stpy_kmv_workspace_bytes": (_i64, [_i32, _i64, _i64, _i32, _i64]),
@@ -555,6 +564,86 @@ def experts_combine_grad(mode, mu_e, var_e, gmu_e, gvar_e, kappa, mu, var, dmu, 
 		raise StpyHipError("experts_combine_grad: gmu_e / gvar_e and dmu / dstd must share their strides")
 	_launch("stpy_experts_combine_grad", int(mode), mu_e.shape[0], mu_e.shape[1], gmu_e.shape[2], ptr(mu_e), ptr(var_e), ld(mu_e), ptr(gmu_e), ptr(gvar_e),
 			ldg, lde, float(kappa), ptr(mu), ptr(var), ptr(dmu), ptr(dstd), ld(dmu))
+
+
+def experts_route_max_k():
+	"""Largest k stpy_experts_route selects."""
+	return int(load().stpy_experts_route_max_k())
+
+
+def experts_centroids(xs, offsets, inv_ls, cols=None):
+	"""cent (E, d): every expert's mean point in scaled coordinates x[cols] * inv_ls, +inf for an expert without rows; one launch
+	(stpy_experts_centroids in the header)."""
+	N, d, E = xs.shape[0], _ncols(xs, cols), offsets.numel() - 1
+	cent = torch.empty((E, d), dtype=torch.float64, device=xs.device)
+	_launch("stpy_experts_centroids", dtype_code(xs.dtype), ptr(xs), N, ld(xs), d, ptr(cols), ptr(offsets), E, ptr(inv_ls), ptr(cent), ld(cent))
+	return cent
+
+
+def experts_route(cent, inv_ls, xt, k, cols=None):
+	"""sel (M, k) int32: the k experts whose centroids are nearest to every test point, ties to the lower id, each row ascending in expert id;
+	one launch (stpy_experts_route in the header)."""
+	E, d, M = cent.shape[0], cent.shape[1], xt.shape[0]
+	sel = torch.empty((M, int(k)), dtype=torch.int32, device=xt.device)
+	_launch("stpy_experts_route", dtype_code(cent.dtype), ptr(cent), ld(cent), E, d, ptr(cols), ptr(inv_ls), ptr(xt), M, ld(xt), int(k), ptr(sel))
+	return sel
+
+
+def experts_route_tiles(E, M, k):
+	"""The host-side bound on the tiles of a routed work list: floor(M k / 32) + min(E, M k)."""
+	return (int(M) * int(k)) // 32 + min(int(E), int(M) * int(k))
+
+
+def experts_work_list(sel, E):
+	"""(wexp (T,), wpair (32 T,)) int32, T = experts_route_tiles: the work list of a routed prediction from sel (M, k), built on the device with
+	integer tensor operations and no read-back.  The pair ids p = t k + j, stably sorted by expert (so test points ascend within an expert), are
+	cut into tiles of 32 per expert; unused tiles carry expert -1, empty columns pair -1."""
+	M, k = sel.shape
+	P, T, dev = M * k, experts_route_tiles(E, M, k), sel.device
+	e = sel.reshape(-1).long()
+	order = torch.argsort(e, stable=True)
+	cnt = torch.zeros((E,), dtype=torch.int64, device=dev).scatter_add_(0, e, torch.ones_like(e))
+	tiles = (cnt + 31) // 32
+	tstart, pstart = torch.cumsum(tiles, 0) - tiles, torch.cumsum(cnt, 0) - cnt
+	es = e[order]
+	rank = torch.arange(P, dtype=torch.int64, device=dev) - pstart[es]
+	tile = tstart[es] + rank // 32
+	wexp = torch.full((T,), -1, dtype=torch.int32, device=dev)
+	wpair = torch.full((T * 32,), -1, dtype=torch.int32, device=dev)
+	wexp[tile] = es.int()
+	wpair[tile * 32 + rank % 32] = order.int()
+	return wexp, wpair
+
+
+def experts_predict_routed_workspace(nmax, d, T, like, grad=False):
+	"""Scratch of stpy_experts_predict_routed (grad: of _predict_routed_grad) for a work list of T tiles; dead after the call."""
+	query = load().stpy_experts_predict_routed_grad_workspace_bytes if grad else load().stpy_experts_predict_routed_workspace_bytes
+	return _work(max(int(query(F64, int(nmax), d, int(T))), 16), like)
+
+
+def experts_predict_routed(kind, xs, offsets, nmax, inv_ls, kappa, factor, alpha, info, xt, wexp, wpair, mu_s, var_s, cols=None, work=None):
+	"""mu_s[j, t], var_s[j, t] (k x M, row stride ld): the prediction of the expert in slot j of test point t's selection, for the pairs the work
+	list (experts_work_list) holds; one launch (stpy_experts_predict_routed in the header)."""
+	N, d, E, M, k, T = xs.shape[0], _ncols(xs, cols), offsets.numel() - 1, xt.shape[0], mu_s.shape[0], wexp.numel()
+	if work is None:
+		work = experts_predict_routed_workspace(nmax, d, T, xs)
+	_launch("stpy_experts_predict_routed", kind, dtype_code(xs.dtype), ptr(xs), N, ld(xs), d, ptr(cols), ptr(offsets), E, int(nmax), ptr(inv_ls), float(kappa),
+			ptr(factor), factor.numel(), ptr(alpha), ptr(info), ptr(xt), M, ld(xt), k, ptr(wexp), ptr(wpair), T, ptr(mu_s), ptr(var_s), ld(mu_s),
+			ptr(work), work.numel())
+
+
+def experts_predict_routed_grad(kind, xs, offsets, nmax, inv_ls, kappa, factor, alpha, info, xt, wexp, wpair, mu_s, var_s, gmu_s, gvar_s, cols=None, work=None):
+	"""experts_predict_routed plus the input gradients gmu_s, gvar_s (k, M, d) over the selected coordinates, one launch
+	(stpy_experts_predict_routed_grad in the header)."""
+	N, d, E, M, k, T = xs.shape[0], _ncols(xs, cols), offsets.numel() - 1, xt.shape[0], mu_s.shape[0], wexp.numel()
+	if work is None:
+		work = experts_predict_routed_workspace(nmax, d, T, xs, grad=True)
+	ldg, lde = _grad_strides(gmu_s)
+	if (ldg, lde) != _grad_strides(gvar_s):
+		raise StpyHipError("experts_predict_routed_grad: gmu_s and gvar_s must share their strides")
+	_launch("stpy_experts_predict_routed_grad", kind, dtype_code(xs.dtype), ptr(xs), N, ld(xs), d, ptr(cols), ptr(offsets), E, int(nmax), ptr(inv_ls),
+			float(kappa), ptr(factor), factor.numel(), ptr(alpha), ptr(info), ptr(xt), M, ld(xt), k, ptr(wexp), ptr(wpair), T, ptr(mu_s), ptr(var_s),
+			ld(mu_s), ptr(gmu_s), ptr(gvar_s), ldg, lde, ptr(work), work.numel())
 
 
 def pchol(kind, x, inv_ls, m, cols=None, kappa=1.0, tol=0.0, ldf=None):

@@ -16,7 +16,31 @@ What runs where
   the same two with input gradients (mean_std_grad, ucb_optimize):
     per-expert mean, variance and their gradients, w = K_e^-1 k*      stpy_experts_predict_grad  (same grid; two triangular MFMA products)
     combination and its chain rule (clamp, rBCM's weights)            stpy_experts_combine_grad  (one thread per test point)
-Python partitions (numpy, host), gathers the points by expert (one device index_select), sequences those launches and owns the tensors.
+  routed prediction (``predict_experts=k``):
+    every expert's centroid in scaled coordinates, once per fit       stpy_experts_centroids     (one wave per expert)
+    the k nearest experts of every test point                         stpy_experts_route         (one wave per test point)
+    the selected experts' predictions (and gradients), k slots        stpy_experts_predict_routed(_grad)  (one workgroup per tile of a work list)
+    combination over the k slots                                      stpy_experts_combine(_grad), unchanged, with E := k
+Python partitions (numpy on the host; "kdtree": torch sorts and segment reductions on the device, level by level), gathers the points by expert
+(one device index_select), builds the routed work lists (device integer operations, no read-back), sequences those launches and owns the tensors.
+
+Spatial partition and routing.  ``partition="kdtree"`` cuts the data into the balanced sizes of "random" as the leaves of a k-d tree over the
+kernel's scaled coordinates x[:, cols] / lengthscale (the rule: ``kdtree_order``), taken with the lengthscales current at ``fit_gp``;
+``log_marginal`` and ``optimize_params`` work on the current partition and the refit at the end of ``optimize_params`` repartitions.  With
+``predict_experts=k`` every prediction (``mean_std`` / ``mean_var`` / ``mean`` / ``ucb`` / ``lcb``, ``mean_std_grad``, ``ucb_optimize``) asks only
+the k experts whose centroids are nearest to the test point (``route``): k M (expert, point) pairs in place of E M, whatever N is; a value above E
+means all experts, a value above the routing kernel's cap of 16 with more than 16 experts is refused.  The combination then runs over the k
+slots: gPoE's beta is 1 / k and BCM's correction (1 - k) / kappa.  Three launches per chunk (route, routed prediction, combination) in place of
+two; a fit makes one more (the centroids).  ``expert_mean_var`` / ``expert_mean_var_grad`` stay all-experts diagnostics.  Routing works with
+every partition but is ACCURATE only on a spatial one: under rBCM a far expert returns var_e ~ kappa and weighs ~ 0, which is what makes it
+safe to skip -- and on a random partition no expert is far.  RMSE against the noiseless f = sin(6 x_0) cos(5 x_1) + 0.5 x_{d-1} on the unit
+cube, 300 test points, SE kernel, rBCM (tests/test_experts_route_cpu.py, NumPy oracle):
+    case                                      random, all E   random, k = 4   kdtree, all E   kdtree, k = 4
+    N 2048, d 2, size 64, ls .15, s .1            .0200           .0525           .0268           .0269
+    N 2048, d 3, size 64, ls .30, s .1            .0483           .0704           .0354           .0357
+    N 1000, d 2, size 48, ls .15, s .05           .0207           .0358           .0205           .0206
+The routed posterior is piecewise smooth: it jumps where the k-th and the (k + 1)-th nearest expert of a point swap, and ``mean_std_grad`` is
+the gradient of the function computed WITH THE SELECTION HELD FIXED.
 
 The hyper-parameters are shared by all experts; the kernel is ONE stationary term (SE / Matern 1/2, 3/2, 5/2, isotropic or ARD, on a column
 group or on all columns), float64 only.  Variances are those of the latent f (no noise term), as in the dense class; like every ``mean_std`` /
@@ -27,8 +51,8 @@ rBCM weights included -- and ``ucb_optimize`` climbs the acquisition from all it
 evaluation and chunk.
 
 Out of scope (refused with the reason): autograd through a test tensor with ``requires_grad`` (use ``mean_std_grad``), ``ucb_optimize`` before a
-fit, spatial partitions beyond a user-given assignment, appending and deleting points, float32, an explicit ``Sigma``, composite kernels,
-several GPUs.
+fit, spatial partitions other than "kdtree" and a user-given assignment (k-means), routing by anything but centroid distance, overlapping or
+hierarchical experts, appending and deleting points, float32, an explicit ``Sigma``, composite kernels, several GPUs.
 """
 import numpy as np
 import torch
@@ -38,6 +62,7 @@ from ..estimator import Estimator
 from ..kernels import KernelFunction
 from .nystrom_fea import _check_term_overrides, _stationary_term
 
+ROUTE_CAP = 16                       # stpy_experts_route_max_k(): checked against the library at the first fit with predict_experts
 EXPERT_CAP = 512                     # stpy_experts_max_n(): checked against the library at the first fit (the constructor stays on the host)
 COMBINE_MODES = {"poe": 0, "gpoe": 1, "bcm": 2, "rbcm": 3}
 # test points of one predict launch: E * chunk stays at or below this many (mu_e, var_e) elements; the launch's workspace is 8 * 32 * ceil(chunk / 32)
@@ -55,15 +80,58 @@ def balanced_sizes(n, expert_size):
 	return np.asarray([base + 1] * extra + [base] * (E - extra), dtype=np.int64)
 
 
-def partition_points(n, expert_size, partition="random", seed=0):
+def kdtree_order(z, sizes):
+	"""The k-d partition of the points z (n, d) -- scaled coordinates x[:, cols] * inv_ls, a tensor on any device -- into len(sizes) leaves of the
+	given sizes, left to right; returns the point indices leaf by leaf (int64, on z's device), ascending within a leaf.  A node owns the leaves
+	[a, b) and a set of points: with b - a == 1 it is that leaf; otherwise mid = a + ceil((b - a) / 2), the split coordinate is the one with the
+	largest max z - min z over the node's points (ties: the lowest position), the points are sorted by (z in that coordinate, original index), the
+	first sum(sizes[a:mid]) go left and the rest right.  Run level by level, ceil(log2 E) of them, every node of a level at once: per level a
+	segment max / min (scatter_reduce), two stable sorts and a gather on the device, and O(E) index arithmetic on the host."""
+	sizes = np.asarray(sizes, dtype=np.int64)
+	n, d, dev = int(z.shape[0]), int(z.shape[1]), z.device
+	csum = np.concatenate([[0], np.cumsum(sizes)])
+	a, b = np.zeros(1, dtype=np.int64), np.full(1, len(sizes), dtype=np.int64)
+	node = torch.zeros((n,), dtype=torch.int64, device=dev)          # the node of every point, in the order of the data
+	iota, pos_d = torch.arange(n, dtype=torch.int64, device=dev), torch.arange(d, dtype=torch.int64, device=dev)
+	while n and np.any(b - a > 1):
+		nn = len(a)
+		split = b - a > 1
+		mid = np.where(split, a + (b - a + 1) // 2, b)
+		left = torch.from_numpy(csum[mid] - csum[a]).to(dev)                    # points that stay left (a leaf keeps all of its points)
+		first = np.concatenate([[0], np.cumsum(1 + split.astype(np.int64))])[:-1]          # the left child's number on the next level
+		idx = node.unsqueeze(1).expand(n, d).contiguous()
+		hi = torch.full((nn, d), -float("inf"), dtype=z.dtype, device=dev).scatter_reduce_(0, idx, z, "amax", include_self=True)
+		lo = torch.full((nn, d), float("inf"), dtype=z.dtype, device=dev).scatter_reduce_(0, idx, z, "amin", include_self=True)
+		spread = hi - lo
+		coord = torch.where(spread == spread.max(dim=1, keepdim=True).values, pos_d, d).min(dim=1).values.clamp_(max=d - 1)
+		key = z.gather(1, coord[node].unsqueeze(1)).squeeze(1)
+		o1 = torch.argsort(key, stable=True)                                    # by (key, original index) ...
+		order = o1[torch.argsort(node[o1], stable=True)]                       # ... within every node
+		ns = node[order]
+		start = torch.from_numpy(csum[a]).to(dev)
+		right = (iota - start[ns]) >= left[ns]
+		node = torch.empty_like(node).scatter_(0, order, torch.from_numpy(first).to(dev)[ns] + right.long())
+		na, nb = np.empty(nn + int(split.sum()), dtype=np.int64), np.empty(nn + int(split.sum()), dtype=np.int64)
+		na[first], nb[first] = a, mid
+		na[first[split] + 1], nb[first[split] + 1] = mid[split], b[split]
+		a, b = na, nb
+	return torch.argsort(node, stable=True)
+
+
+def partition_points(n, expert_size, partition="random", seed=0, z=None):
 	"""(order, sizes): ``order`` lists the point indices expert by expert, ``sizes[e]`` is the number of points of expert e.  "random": a
-	numpy.random.default_rng(seed) permutation cut into balanced pieces; "contiguous": the given order cut the same way; an integer array /
-	tensor of n expert ids: the points of expert e in their given order, E = largest id + 1."""
+	numpy.random.default_rng(seed) permutation cut into balanced pieces; "contiguous": the given order cut the same way; "kdtree": the same
+	sizes, left to right, as the leaves of a k-d tree over the scaled coordinates ``z`` (n, d) (``kdtree_order``); an integer array / tensor of
+	n expert ids: the points of expert e in their given order, E = largest id + 1."""
 	n = int(n)
 	if isinstance(partition, str):
-		if partition not in ("random", "contiguous"):
-			raise ValueError("LocalExpertsGaussianProcess: partition=%r (\"random\", \"contiguous\" or an integer tensor of expert ids)" % (partition,))
+		if partition not in ("random", "contiguous", "kdtree"):
+			raise ValueError("LocalExpertsGaussianProcess: partition=%r (\"random\", \"contiguous\", \"kdtree\" or an integer tensor of expert ids)" % (partition,))
 		sizes = balanced_sizes(n, expert_size)
+		if partition == "kdtree" and n > 0:
+			if z is None or int(z.shape[0]) != n:
+				raise ValueError("LocalExpertsGaussianProcess: partition=\"kdtree\" needs the scaled coordinates z of the n points")
+			return kdtree_order(z, sizes).cpu().numpy().astype(np.int64), sizes
 		order = np.random.default_rng(int(seed)).permutation(n) if partition == "random" else np.arange(n)
 		return order.astype(np.int64), sizes
 	ids = partition.detach().cpu().numpy() if torch.is_tensor(partition) else np.asarray(partition)
@@ -95,7 +163,7 @@ class _ExpertsEvidenceFn(torch.autograd.Function):
 class LocalExpertsGaussianProcess(Estimator):
 
 	def __init__(self, gamma=1, s=0.001, kappa=1., kernel_name="squared_exponential", d=1, kernel=None, nu=1.5, expert_size=256,
-				 partition="random", partition_seed=0, combine="rbcm", max_size=10000, bounds=None):
+				 partition="random", partition_seed=0, combine="rbcm", max_size=10000, predict_experts=None, bounds=None):
 		self.s = s
 		self.d = d
 		self.bounds = bounds                             # box of ucb_optimize: a (low, high) per coordinate
@@ -112,11 +180,15 @@ class LocalExpertsGaussianProcess(Estimator):
 		self.kernel = self.kernel_object.kernel
 		self.expert_size, self.partition, self.partition_seed = int(expert_size), partition, int(partition_seed)
 		self.combine, self.max_size = combine, int(max_size)
+		self.predict_experts = predict_experts           # None: every expert predicts everywhere; k: a test point asks its k nearest experts
 		self.assignment_ = self.offsets_ = None          # host arrays: expert id of every point (given order), row range of every expert (gathered order)
-		self.launches = 0                                # kernel launches of this object so far (a fit is 2, a prediction chunk is 2)
+		# kernel launches of this object so far: a fit is 2 and a prediction chunk is 2; with predict_experts a fit is 3 (the centroids) and a
+		# chunk is 3 (route, routed prediction, combination)
+		self.launches = 0
 		self.lml_batch_path = "device"
 		self._sizes, self._order = np.zeros((0,), dtype=np.int64), None
 		self._xs = self._ys = self._offsets = self._factor = self._alpha = self._info = self._hyper = None
+		self._cent, self._k = None, 0                    # the experts' centroids in scaled coordinates and min(predict_experts, E), set by a fit
 		self._check()
 
 	# ------------------------------------------------------------------ host checks
@@ -132,8 +204,11 @@ class LocalExpertsGaussianProcess(Estimator):
 							 % (self.expert_size, EXPERT_CAP))
 		if self.combine not in COMBINE_MODES:
 			raise ValueError("LocalExpertsGaussianProcess: combine=%r, one of %s" % (self.combine, ", ".join(repr(k) for k in COMBINE_MODES)))
-		if isinstance(self.partition, str) and self.partition not in ("random", "contiguous"):
-			raise ValueError("LocalExpertsGaussianProcess: partition=%r (\"random\", \"contiguous\" or an integer tensor of expert ids)" % (self.partition,))
+		if isinstance(self.partition, str) and self.partition not in ("random", "contiguous", "kdtree"):
+			raise ValueError("LocalExpertsGaussianProcess: partition=%r (\"random\", \"contiguous\", \"kdtree\" or an integer tensor of expert ids)" % (self.partition,))
+		k = self.predict_experts
+		if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1):
+			raise ValueError("LocalExpertsGaussianProcess: predict_experts=%r (None: all experts, or the number k >= 1 of nearest experts a test point asks)" % (k,))
 		if self.max_size < 1:
 			raise ValueError("LocalExpertsGaussianProcess: max_size must be positive")
 
@@ -149,10 +224,16 @@ class LocalExpertsGaussianProcess(Estimator):
 
 	@property
 	def experts_info(self):
-		"""E, the experts' sizes, the kernel launches so far and the bytes of the resident factor buffer (host bookkeeping only)."""
+		"""E, the experts' sizes, the kernel launches so far and the bytes of the resident factor buffer (host bookkeeping only).  An object that
+		opted into the k-d partition or into routing also reports "partition" (its name; "given" for an id array) and "predict_experts" (as
+		given; the number in use is min(predict_experts, E))."""
 		E = int(len(self._sizes))
 		npm = -(-int(self._sizes.max()) // 32) * 32 if E else 0
-		return {"E": E, "sizes": [int(v) for v in self._sizes], "launches": int(self.launches), "factor_bytes": 8 * E * npm * npm if self.fitted else 0}
+		info = {"E": E, "sizes": [int(v) for v in self._sizes], "launches": int(self.launches), "factor_bytes": 8 * E * npm * npm if self.fitted else 0}
+		if self.predict_experts is not None or (isinstance(self.partition, str) and self.partition == "kdtree"):
+			info.update(partition=self.partition if isinstance(self.partition, str) else "given",
+						predict_experts=None if self.predict_experts is None else int(self.predict_experts))
+		return info
 
 	def add_data_point(self, *args, **kwargs):
 		raise NotImplementedError("LocalExpertsGaussianProcess.add_data_point: appending to a fitted committee is not implemented; refit")
@@ -175,8 +256,15 @@ class LocalExpertsGaussianProcess(Estimator):
 			raise NotImplementedError("LocalExpertsGaussianProcess: float32 data; the expert kernels are float64 only (a 512-point Cholesky in "
 									  "one workgroup has no fp32 route)")
 
-	def _partition(self, n):
-		order, sizes = partition_points(n, self.expert_size, self.partition, self.partition_seed)
+	def _partition(self, n, x=None):
+		z = None
+		if isinstance(self.partition, str) and self.partition == "kdtree" and n:
+			# scaled coordinates under the lengthscales current now, on the device where the data are: one multiplication per entry
+			xd = _lib.to_device(x, torch.float64)
+			term = _stationary_term(self.kernel_object)
+			cols, inv_ls = self.kernel_object._term_operands(term, xd, xd.dtype, xd.device)
+			z = (xd if cols is None else xd.index_select(1, cols.long())) * inv_ls
+		order, sizes = partition_points(n, self.expert_size, self.partition, self.partition_seed, z=z)
 		over = np.nonzero(sizes > EXPERT_CAP)[0]
 		if over.size:
 			raise ValueError("LocalExpertsGaussianProcess: expert %d has %d points, above the cap of %d (stpy_experts_max_n)"
@@ -187,11 +275,15 @@ class LocalExpertsGaussianProcess(Estimator):
 		self._check()
 		self._check_data(x, Sigma)
 		n = int(x.shape[0])
-		order, sizes = self._partition(n)          # (host; an oversized expert is refused before anything reaches the device)
+		order, sizes = self._partition(n, x)       # (host, but "kdtree"; an oversized expert is refused before anything reaches the device)
+		k = self.predict_experts
+		if k is not None and k > ROUTE_CAP and len(sizes) > ROUTE_CAP:
+			raise ValueError("LocalExpertsGaussianProcess: predict_experts=%d with %d experts: the routing kernel selects at most %d "
+							 "(stpy_experts_route_max_k; a value above the number of experts means all of them)" % (k, len(sizes), ROUTE_CAP))
 		self.n, self.d = x.shape
 		self.x, self.y = x, y
 		self.fitted = False
-		self._factor = self._alpha = self._info = None
+		self._factor = self._alpha = self._info = self._cent = None
 		offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
 		assignment = np.empty(n, dtype=np.int64)
 		assignment[order] = np.repeat(np.arange(len(sizes)), sizes)
@@ -215,6 +307,12 @@ class LocalExpertsGaussianProcess(Estimator):
 		self._raise_failed(packed.cpu().numpy()[-4 * E:].view(np.int32), "fit_gp")          # the one read-back of a fit (waits for the launch)
 		self._factor, self._alpha, self._info = factor, alpha, info
 		self._hyper = (term['kind'], float(term['kappa']), cols, inv_ls, nmax)
+		if self.predict_experts is not None:          # the centroids, once per fit
+			if _lib.experts_route_max_k() < ROUTE_CAP:
+				raise _lib.StpyHipError("libstpy_hip.so routes to %d experts, the package expects %d" % (_lib.experts_route_max_k(), ROUTE_CAP))
+			self._k = min(int(self.predict_experts), E)
+			self._cent = _lib.experts_centroids(self._xs, self._offsets, inv_ls, cols=cols)
+			self.launches += 1
 		self.fitted = True
 		return None
 
@@ -274,7 +372,82 @@ class LocalExpertsGaussianProcess(Estimator):
 		mu_e, var_e = self._experts_device(_lib.to_device(xtest, torch.float64))
 		return _lib.like_input(mu_e, xtest), _lib.like_input(var_e, xtest)
 
+	# ------------------------------------------------------------------ routing
+	def _routed_chunks(self, m, per_pair=1):
+		"""The routed paths' rule: k * chunk * per_pair output elements stay at or below PREDICT_BUDGET (per_pair = 1 for a prediction's pairs,
+		2 + 2 d with gradients); a chunk's work list has at most chunk k / 32 + min(E, chunk k) tiles of 8 * 32 * (largest expert rounded up
+		to 32) bytes of workspace each, twice that with gradients."""
+		step = max(1, min(self.max_size, PREDICT_BUDGET // (self._k * per_pair)))
+		return [(a, min(a + step, m)) for a in range(0, m, step)]
+
+	def _route_device(self, xt):
+		"""sel (M, k) int32 on the device: one stpy_experts_route launch."""
+		kind, kappa, cols, inv_ls, nmax = self._hyper
+		sel = _lib.experts_route(self._cent, inv_ls, xt, self._k, cols=cols)
+		self.launches += 1
+		return sel
+
+	def route(self, xtest):
+		"""The experts a routed prediction asks: an (M, k) integer tensor of expert ids, k = min(predict_experts, E), ascending in every row,
+		placed like ``xtest`` -- the k experts whose centroids (means of their points in the kernel's scaled coordinates) are nearest to the
+		test point, ties going to the lower id, experts without points last.  One launch per chunk of ``max_size`` points."""
+		self._no_grad(xtest)
+		if self.predict_experts is None:
+			raise ValueError("LocalExpertsGaussianProcess.route: the object was made with predict_experts=None (every expert predicts everywhere)")
+		if not self.fitted:
+			raise AttributeError("LocalExpertsGaussianProcess.route needs a fitted object: call fit_gp first")
+		xt = _lib.to_device(xtest, torch.float64)
+		m = xt.shape[0]
+		sel = torch.empty((m, self._k), dtype=torch.int32, device=xt.device)
+		for a, b in self._routed_chunks(m):
+			sel[a:b] = self._route_device(xt[a:b])
+		return _lib.like_input(sel.long(), xtest)
+
+	def _mean_var_routed(self, xt):
+		"""``_mean_var_device`` with routing: per chunk stpy_experts_route, the work list (device integer operations, no read-back),
+		stpy_experts_predict_routed into (k, chunk) slots and stpy_experts_combine over the k slots: three launches."""
+		kind, kappa, cols, inv_ls, nmax = self._hyper
+		E, k, m, d = len(self._sizes), self._k, xt.shape[0], inv_ls.numel()
+		mu = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		var = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		chunks = self._routed_chunks(m)
+		work = _lib.experts_predict_routed_workspace(nmax, d, _lib.experts_route_tiles(E, max(b - a for a, b in chunks), k), xt) if chunks else None
+		for a, b in chunks:
+			wexp, wpair = _lib.experts_work_list(self._route_device(xt[a:b]), E)
+			mu_s = torch.empty((k, b - a), dtype=torch.float64, device=xt.device)
+			var_s = torch.empty((k, b - a), dtype=torch.float64, device=xt.device)
+			_lib.experts_predict_routed(kind, self._xs, self._offsets, nmax, inv_ls, kappa, self._factor, self._alpha, self._info, xt[a:b], wexp, wpair,
+										mu_s, var_s, cols=cols, work=work)
+			_lib.experts_combine(COMBINE_MODES[self.combine], mu_s, var_s, kappa, mu[a:b], var[a:b])
+			self.launches += 2
+		return mu, var
+
+	def _mean_var_grad_routed(self, xt):
+		"""``_mean_var_grad_device`` with routing: per chunk stpy_experts_route, the work list, stpy_experts_predict_routed_grad and
+		stpy_experts_combine_grad over the k slots: three launches.  The selection is held fixed under the derivative."""
+		kind, kappa, cols, inv_ls, nmax = self._hyper
+		E, k, m, d = len(self._sizes), self._k, xt.shape[0], inv_ls.numel()
+		mu = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		var = torch.empty((m,), dtype=torch.float64, device=xt.device)
+		dmu = torch.empty((m, d), dtype=torch.float64, device=xt.device)
+		dstd = torch.empty((m, d), dtype=torch.float64, device=xt.device)
+		chunks = self._routed_chunks(m, 2 + 2 * d)
+		work = _lib.experts_predict_routed_workspace(nmax, d, _lib.experts_route_tiles(E, max(b - a for a, b in chunks), k), xt, grad=True) if chunks else None
+		for a, b in chunks:
+			wexp, wpair = _lib.experts_work_list(self._route_device(xt[a:b]), E)
+			mu_s = torch.empty((k, b - a), dtype=torch.float64, device=xt.device)
+			var_s = torch.empty((k, b - a), dtype=torch.float64, device=xt.device)
+			gmu_s = torch.empty((k, b - a, d), dtype=torch.float64, device=xt.device)
+			gvar_s = torch.empty((k, b - a, d), dtype=torch.float64, device=xt.device)
+			_lib.experts_predict_routed_grad(kind, self._xs, self._offsets, nmax, inv_ls, kappa, self._factor, self._alpha, self._info, xt[a:b], wexp, wpair,
+											 mu_s, var_s, gmu_s, gvar_s, cols=cols, work=work)
+			_lib.experts_combine_grad(COMBINE_MODES[self.combine], mu_s, var_s, gmu_s, gvar_s, kappa, mu[a:b], var[a:b], dmu[a:b], dstd[a:b])
+			self.launches += 2
+		return mu, var, dmu, dstd
+
 	def _mean_var_device(self, xt):
+		if self._cent is not None:
+			return self._mean_var_routed(xt)
 		kind, kappa, cols, inv_ls, nmax = self._hyper
 		E, m = len(self._sizes), xt.shape[0]
 		mu = torch.empty((m,), dtype=torch.float64, device=xt.device)
@@ -357,6 +530,8 @@ class LocalExpertsGaussianProcess(Estimator):
 	def _mean_var_grad_device(self, xt):
 		"""(mu, var (M,), dmu, dstd (M, d) over the selected coordinates): per chunk one stpy_experts_predict_grad and one
 		stpy_experts_combine_grad launch.  mu and var carry the bits of ``_mean_var_device``."""
+		if self._cent is not None:
+			return self._mean_var_grad_routed(xt)
 		kind, kappa, cols, inv_ls, nmax = self._hyper
 		E, m, d = len(self._sizes), xt.shape[0], inv_ls.numel()
 		mu = torch.empty((m,), dtype=torch.float64, device=xt.device)
@@ -396,7 +571,9 @@ class LocalExpertsGaussianProcess(Estimator):
 		"""GaussianProcess.ucb_optimize on the committee: maximise mu + sqrt(beta) sigma (mu - sqrt(beta) sigma with ``lcb``) over ``self.bounds``
 		from ``multistart`` uniform starts drawn with the reference's np.random calls in its order.  All starts are ONE stacked L-BFGS-B problem
 		(``_multistart_maximize`` of gauss_procc.py); every evaluation is one stpy_experts_predict_grad and one stpy_experts_combine_grad launch
-		per chunk of starts.  Returns (solution (d,), value) of the best start, never below the acquisition at any drawn start.
+		per chunk of starts (with ``predict_experts``: three -- stpy_experts_route, stpy_experts_predict_routed_grad, stpy_experts_combine_grad --
+		so ``launches`` is three times ``evaluations`` where one chunk holds the starts; every evaluation routes anew, and the gradient holds
+		that selection fixed).  Returns (solution (d,), value) of the best start, never below the acquisition at any drawn start.
 		``self.optimize_info``: starts, start_values, evaluations, launches."""
 		from .gauss_procc import _draw_starts, _multistart_maximize
 		if not self.fitted:

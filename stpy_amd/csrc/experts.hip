@@ -1,4 +1,5 @@
-// Local GP experts (stpy_experts_fit / _predict / _combine / _predict_grad / _combine_grad; LocalExpertsGaussianProcess): E exact GPs on E different blocks of the data under ONE
+// Local GP experts (stpy_experts_fit / _predict / _combine / _predict_grad / _combine_grad, and the routed prediction stpy_experts_centroids /
+// _route / _predict_routed / _predict_routed_grad; LocalExpertsGaussianProcess): E exact GPs on E different blocks of the data under ONE
 // hyper-parameter candidate, the mirror image of the batched evidence (reduce.hip: B candidates on the same data), from the same one-workgroup
 // building blocks (lb_block.h).
 //
@@ -22,6 +23,8 @@
 // w = K^-1 k* = V v by lb_panel<0> as it stands (A = V upper triangular from its row 0), then d mu / dx and d var / dx from direct differences,
 // one wave per test point; workspace two slices of 32 NPM doubles per (expert, tile).  The combination differentiates what it computes: the clamp
 // (zero where active) and rBCM's variance-dependent weights.
+// Routed prediction (further down): the same bodies on a work list of (expert, 32 pairs) tiles in place of the grid of (expert, tile) -- a tile is
+// known to the bodies only through ExpertsTileDense / ExpertsTileRouted: which test point a column reads and where its results go.
 // Every sum has a fixed order and no workgroup reads what another wrote: an expert's outputs are bit-identical wherever it sits in whatever batch.
 // Compiled inside api.hip (which includes this file, as it includes pchol.hip and the kmv family; it also compiles on its own, as the resource
 // test does) and NOT beside lml_batch_kernel in reduce.hip: more kernels in that translation unit change its LDS layout and with it its instructions.
@@ -104,13 +107,36 @@ void experts_total_kernel(const double* value, const double* grad, int64_t ldg, 
 	}
 }
 
-// Steps 1 - 3 of a prediction for one (expert, tile): the ONE body of experts_predict_kernel and experts_predict_grad_kernel, so that the two write
-// the same bits to mu and var.  x, al, V: the expert's rows, its alpha and its factor slice; n of them, NP = n rounded up to 32; KT: 32 x NP doubles
+// What column t of a tile stands for: the test point it reads (row(t), -1: an empty column) and where its results go (out(t) into mu / var,
+// gout(t) into the gradient arrays).  The body below knows a tile only through one of these two.
+//   ExpertsTileDense    the tile of the all-experts kernels: 32 consecutive test points from t0, mt of them in range; mu, var, gmu, gvar are the
+//                       caller's pointers at (e, t0)
+//   ExpertsTileRouted   a tile of the work list of the routed kernels: trow / oidx / gidx are 32-entry tables in LDS (experts_routed_tile fills
+//                       them from wpair); mu, var, gmu, gvar are the caller's array bases
+struct ExpertsTileDense {
+	int64_t t0; int mt; int64_t ldg;
+	__device__ __forceinline__ bool has(int t) const { return t < mt; }
+	__device__ __forceinline__ int64_t row(int t) const { return t0 + t; }
+	__device__ __forceinline__ int64_t out(int t) const { return t; }
+	__device__ __forceinline__ int64_t gout(int t) const { return (int64_t)t * ldg; }
+};
+
+struct ExpertsTileRouted {
+	const int64_t* trow; const int64_t* oidx; const int64_t* gidx;
+	__device__ __forceinline__ bool has(int t) const { return trow[t] >= 0; }
+	__device__ __forceinline__ int64_t row(int t) const { return trow[t]; }
+	__device__ __forceinline__ int64_t out(int t) const { return oidx[t]; }
+	__device__ __forceinline__ int64_t gout(int t) const { return gidx[t]; }
+};
+
+// Steps 1 - 3 of a prediction for one (expert, tile): the ONE body of experts_predict_kernel, experts_predict_grad_kernel and their routed twins,
+// so that the four write the same bits to mu and var (every sum below runs over k for one fixed column: a column's results do not depend on
+// which tile, or which column of it, it sits in).  x, al, V: the expert's rows, its alpha and its factor slice; n of them, NP = n rounded up to 32; KT: 32 x NP doubles
 // of workspace.  With STORE_V the accumulators of step 3 are also written out, VT[t][k] = (L^-1 k*_t)_k for all 32 t and k < NP (zero for t >= mt and
 // k >= n): what the variance gradient's second triangular product reads.  As, Bs, ssq: the caller's LDS.  Entered and left by the whole workgroup.
-template <bool STORE_V>
+template <bool STORE_V, class Tile>
 __device__ __forceinline__ void experts_predict_body(const ExpertsPredictArgs& p, const double* x, const double* al, const double* V, int n, int NP,
-                                                     int64_t t0, int mt, double* KT, double* VT, double* mu, double* var,
+                                                     const Tile& tl, double* KT, double* VT, double* mu, double* var,
                                                      double* As, double* Bs, double (*ssq)[EX_TILE])
 {
 	typedef Mfma<double>::v4 v4;
@@ -124,20 +150,21 @@ __device__ __forceinline__ void experts_predict_body(const ExpertsPredictArgs& p
 		const double* xk = x + (int64_t)k * p.ldx;
 		for (int t = 0; t < EX_TILE; ++t) {
 			double v = 0.0;
-			if (k < n && t < mt) v = p.kappa * lb_phi(p.kind, lb_r2(xk, p.xt + (t0 + t) * p.ldt, p.cols, il, p.d));
+			if (k < n && tl.has(t)) v = p.kappa * lb_phi(p.kind, lb_r2(xk, p.xt + tl.row(t) * p.ldt, p.cols, il, p.d));
 			KT[(int64_t)t * ld + k] = v;
 		}
 	}
 	__syncthreads();
 
 	// ---- 2. mu_t = sum_k k*_kt alpha_k: one wave per test point, lanes strided over k, shuffle tree
-	for (int t = w; t < mt; t += 4) {
+	for (int t = w; t < EX_TILE; t += 4) {
+		if (!tl.has(t)) continue;          // (wave-uniform)
 		const double* kr = KT + (int64_t)t * ld;
 		double s = 0.0;
 		for (int k = lane; k < n; k += 64) s = fma(kr[k], al[k], s);
 #pragma unroll
 		for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-		if (lane == 0) mu[t] = s;
+		if (lane == 0) mu[tl.out(t)] = s;
 	}
 
 	// ---- 3. v = L^-1 k* = V^T k*, 64 rows per round, and the column sums of v o v from the accumulators.  Row i of L^-1 ends at column i: the round
@@ -198,7 +225,7 @@ __device__ __forceinline__ void experts_predict_body(const ExpertsPredictArgs& p
 		ssq[w][16 + fr] = q1;
 	}
 	__syncthreads();
-	if (tid < mt) var[tid] = p.kappa - (((ssq[0][tid] + ssq[1][tid]) + ssq[2][tid]) + ssq[3][tid]);
+	if (tid < EX_TILE && tl.has(tid)) var[tl.out(tid)] = p.kappa - (((ssq[0][tid] + ssq[1][tid]) + ssq[2][tid]) + ssq[3][tid]);
 }
 
 // whether expert e has a factor the launch is sized for (workgroup-uniform)
@@ -229,53 +256,18 @@ void experts_predict_kernel(ExpertsPredictArgs p)
 	}
 	const int n = (int)(hi - lo), NP = (n + 31) & ~31;
 	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;          // KT[t][k] = k(xt_{t0 + t}, x_k), zero for t >= mt and k >= n
-	experts_predict_body<false>(p, p.xs + lo * p.ldx, p.alpha + lo, p.factor + (int64_t)e * p.fslice, n, NP, t0, mt, KT, nullptr, mu, var, As, Bs, ssq);
+	experts_predict_body<false>(p, p.xs + lo * p.ldx, p.alpha + lo, p.factor + (int64_t)e * p.fslice, n, NP, ExpertsTileDense{t0, mt, 0}, KT, nullptr, mu, var,
+	                            As, Bs, ssq);
 }
 
-// The prediction with its input gradients, per (expert, tile of 32 test points); the workspace slice is two halves of 32 NPM doubles.
-//   1 - 3. experts_predict_body<true>: mu, var as experts_predict_kernel writes them, and v = L^-1 k* kept: VT[t][k] (second half of the slice);
-//   4. w = K^-1 k* = L^-T v = V v, W[i][t] = sum_{k >= i} V[i][k] VT[t][k]: lb_panel<0> with A = V upper triangular from its row 0 (the round that
-//      starts at row r0 reads V from column r0 on; the block just below the block diagonal is stored as zero, what lies further below is not
-//      read), B = VT, C = W (NP x 32, row stride 32) over the k* tile, which is dead by then;
-//   5. with F = lb_dfactor(r^2), r^2 recomputed from the points (direct differences), per selected column m:
-//        gmu[t][m]  = -kappa il_m^2 sum_k alpha_k F_tk (xt_m - x_km),     gvar[t][m] = 2 kappa il_m^2 sum_k w_tk F_tk (xt_m - x_km)
-//      (d k(x, x) / dx = 0 for a stationary term; Matern 1/2 on a coincident pair: F = 0): one wave per test point, lanes strided over k, a fixed
-//      shuffle tree, four columns per pass over k; the first pass leaves F in VT[t][k] (dead after step 4; each lane re-reads what it stored).
-__global__ __launch_bounds__(256, 2)
-void experts_predict_grad_kernel(ExpertsPredictGradArgs g)
+// Steps 4 - 5 of a prediction with input gradients for one (expert, tile), after experts_predict_body<true> on the same tile: the ONE body of
+// experts_predict_grad_kernel and its routed twin (the numbering is that of the comment on experts_predict_grad_kernel).  gmu, gvar: where
+// tl.gout(t) counts from.  Entered by the whole workgroup.
+template <class Tile>
+__device__ __forceinline__ void experts_grad_body(const ExpertsPredictArgs& p, const double* x, const double* al, const double* V, int n, int NP,
+                                                  const Tile& tl, double* KT, double* VT, double* gmu, double* gvar, double* As, double* Bs)
 {
-	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
-	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
-	__shared__ double ssq[4][EX_TILE];
-	const ExpertsPredictArgs& p = g.p;
 	const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-	const int e = blockIdx.x / p.ntiles, tile = blockIdx.x - e * p.ntiles;
-	const int64_t t0 = (int64_t)tile * EX_TILE;
-	const int mt = (int)min((int64_t)EX_TILE, p.M - t0);
-	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
-	double* mu = p.mu_e + (int64_t)e * p.ldm + t0;
-	double* var = p.var_e + (int64_t)e * p.ldm + t0;
-	double* gmu = g.gmu_e + (int64_t)e * g.lde + t0 * g.ldg;
-	double* gvar = g.gvar_e + (int64_t)e * g.lde + t0 * g.ldg;
-	if (!experts_has_factor(p, e, lo, hi)) {          // (workgroup-uniform) an expert without a factor: the prior, which is flat
-		if (tid < mt) {
-			mu[tid] = 0.0;
-			var[tid] = p.kappa;
-		}
-		for (int i = tid; i < mt * p.d; i += 256) {
-			const int t = i / p.d, m = i - t * p.d;
-			gmu[(int64_t)t * g.ldg + m] = 0.0;
-			gvar[(int64_t)t * g.ldg + m] = 0.0;
-		}
-		return;
-	}
-	const int n = (int)(hi - lo), NP = (n + 31) & ~31;
-	const double* x = p.xs + lo * p.ldx;
-	const double* al = p.alpha + lo;
-	const double* V = p.factor + (int64_t)e * p.fslice;
-	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;          // the k* tile, then W[k][t] = (K^-1 k*_t)_k
-	double* VT = KT + (p.wslice >> 1);                             // VT[t][k] = (L^-1 k*_t)_k, then F_tk
-	experts_predict_body<true>(p, x, al, V, n, NP, t0, mt, KT, VT, mu, var, As, Bs, ssq);
 
 	// ---- 4. W = V VT^T (lb_panel opens with a barrier: the stores of VT, and the last reads of the k* tile, are behind it)
 	lb_panel<0>(KT, EX_TILE, V, NP, VT, NP, NP, NP, 0, As, Bs);
@@ -283,9 +275,12 @@ void experts_predict_grad_kernel(ExpertsPredictGradArgs g)
 
 	// ---- 5. the gradients
 	const double* il = p.inv_ls;
-	for (int t = w; t < mt; t += 4) {
-		const double* xt = p.xt + (t0 + t) * p.ldt;
+	for (int t = w; t < EX_TILE; t += 4) {
+		if (!tl.has(t)) continue;          // (wave-uniform; no barrier below)
+		const double* xt = p.xt + tl.row(t) * p.ldt;
 		double* Ft = VT + (int64_t)t * NP;
+		double* gm = gmu + tl.gout(t);
+		double* gv = gvar + tl.gout(t);
 		for (int m0 = 0; m0 < p.d; m0 += 4) {
 			double sm[4] = {0.0, 0.0, 0.0, 0.0}, sv[4] = {0.0, 0.0, 0.0, 0.0};
 			for (int k = lane; k < n; k += 64) {
@@ -319,12 +314,251 @@ void experts_predict_grad_kernel(ExpertsPredictGradArgs g)
 				for (int c = 0; c < 4; ++c)
 					if (m0 + c < p.d) {
 						const double s2 = p.kappa * (il[m0 + c] * il[m0 + c]);
-						gmu[(int64_t)t * g.ldg + m0 + c] = -(s2 * sm[c]);
-						gvar[(int64_t)t * g.ldg + m0 + c] = 2.0 * (s2 * sv[c]);
+						gm[m0 + c] = -(s2 * sm[c]);
+						gv[m0 + c] = 2.0 * (s2 * sv[c]);
 					}
 			}
 		}
 	}
+}
+
+// The prediction with its input gradients, per (expert, tile of 32 test points); the workspace slice is two halves of 32 NPM doubles.
+//   1 - 3. experts_predict_body<true>: mu, var as experts_predict_kernel writes them, and v = L^-1 k* kept: VT[t][k] (second half of the slice);
+//   4. w = K^-1 k* = L^-T v = V v, W[i][t] = sum_{k >= i} V[i][k] VT[t][k]: lb_panel<0> with A = V upper triangular from its row 0 (the round that
+//      starts at row r0 reads V from column r0 on; the block just below the block diagonal is stored as zero, what lies further below is not
+//      read), B = VT, C = W (NP x 32, row stride 32) over the k* tile, which is dead by then;
+//   5. with F = lb_dfactor(r^2), r^2 recomputed from the points (direct differences), per selected column m:
+//        gmu[t][m]  = -kappa il_m^2 sum_k alpha_k F_tk (xt_m - x_km),     gvar[t][m] = 2 kappa il_m^2 sum_k w_tk F_tk (xt_m - x_km)
+//      (d k(x, x) / dx = 0 for a stationary term; Matern 1/2 on a coincident pair: F = 0): one wave per test point, lanes strided over k, a fixed
+//      shuffle tree, four columns per pass over k; the first pass leaves F in VT[t][k] (dead after step 4; each lane re-reads what it stored).
+__global__ __launch_bounds__(256, 2)
+void experts_predict_grad_kernel(ExpertsPredictGradArgs g)
+{
+	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
+	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
+	__shared__ double ssq[4][EX_TILE];
+	const ExpertsPredictArgs& p = g.p;
+	const int tid = threadIdx.x;
+	const int e = blockIdx.x / p.ntiles, tile = blockIdx.x - e * p.ntiles;
+	const int64_t t0 = (int64_t)tile * EX_TILE;
+	const int mt = (int)min((int64_t)EX_TILE, p.M - t0);
+	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
+	double* mu = p.mu_e + (int64_t)e * p.ldm + t0;
+	double* var = p.var_e + (int64_t)e * p.ldm + t0;
+	double* gmu = g.gmu_e + (int64_t)e * g.lde + t0 * g.ldg;
+	double* gvar = g.gvar_e + (int64_t)e * g.lde + t0 * g.ldg;
+	if (!experts_has_factor(p, e, lo, hi)) {          // (workgroup-uniform) an expert without a factor: the prior, which is flat
+		if (tid < mt) {
+			mu[tid] = 0.0;
+			var[tid] = p.kappa;
+		}
+		for (int i = tid; i < mt * p.d; i += 256) {
+			const int t = i / p.d, m = i - t * p.d;
+			gmu[(int64_t)t * g.ldg + m] = 0.0;
+			gvar[(int64_t)t * g.ldg + m] = 0.0;
+		}
+		return;
+	}
+	const int n = (int)(hi - lo), NP = (n + 31) & ~31;
+	const double* x = p.xs + lo * p.ldx;
+	const double* al = p.alpha + lo;
+	const double* V = p.factor + (int64_t)e * p.fslice;
+	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;          // the k* tile, then W[k][t] = (K^-1 k*_t)_k
+	double* VT = KT + (p.wslice >> 1);                             // VT[t][k] = (L^-1 k*_t)_k, then F_tk
+	const ExpertsTileDense tl{t0, mt, g.ldg};
+	experts_predict_body<true>(p, x, al, V, n, NP, tl, KT, VT, mu, var, As, Bs, ssq);
+	experts_grad_body(p, x, al, V, n, NP, tl, KT, VT, gmu, gvar, As, Bs);
+}
+
+// ---- Routed prediction: each test point asks its k nearest experts only (stpy_experts_centroids / _route / _predict_routed / _predict_routed_grad).
+// The work list (built by the caller, on the device): tile w belongs to expert wexp[w] and its column c to pair wpair[32 w + c] = t k + j -- test
+// point t, slot j of its selection -- or to nobody (-1).  The tile runs the bodies above; its results go to slot j of point t: mu_s[j ldm + t],
+// gmu_s[j lde + t ldg + m], the layout the combination kernels read with E := k.  Whatever the list holds, nothing is written out of bounds: a tile
+// whose expert is outside [0, E) returns at once, a pair outside [0, M k) is an empty column.
+constexpr int EX_ROUTE_K = 16;          // stpy_experts_route_max_k(): a lane of the routing kernel keeps this many candidates in registers
+
+struct ExpertsRouteList { const int32_t* wexp; const int32_t* wpair; int k; int64_t E; };
+
+// the tables of ExpertsTileRouted for tile blockIdx.x; ends with a barrier (entered by the whole workgroup)
+__device__ __forceinline__ void experts_routed_tile(const ExpertsRouteList& r, int64_t M, int64_t ldm, int64_t ldg, int64_t lde,
+                                                    int64_t* trow, int64_t* oidx, int64_t* gidx)
+{
+	const int tid = threadIdx.x;
+	if (tid < EX_TILE) {
+		const int64_t pr = r.wpair[(int64_t)blockIdx.x * EX_TILE + tid];
+		const bool ok = pr >= 0 && pr < M * r.k;
+		const int64_t t = ok ? pr / r.k : 0, j = ok ? pr - t * r.k : 0;
+		trow[tid] = ok ? t : -1;
+		oidx[tid] = j * ldm + t;
+		gidx[tid] = j * lde + t * ldg;
+	}
+	__syncthreads();
+}
+
+__global__ __launch_bounds__(256, 2)
+void experts_predict_routed_kernel(ExpertsPredictArgs p, ExpertsRouteList r)
+{
+	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
+	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
+	__shared__ double ssq[4][EX_TILE];
+	__shared__ int64_t trow[EX_TILE], oidx[EX_TILE], gidx[EX_TILE];
+	const int tid = threadIdx.x;
+	const int e = r.wexp[blockIdx.x];
+	if (e < 0 || e >= r.E) return;          // (workgroup-uniform, before any barrier) a tile the list does not use
+	experts_routed_tile(r, p.M, p.ldm, 0, 0, trow, oidx, gidx);
+	const ExpertsTileRouted tl{trow, oidx, gidx};
+	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
+	if (!experts_has_factor(p, e, lo, hi)) {          // (workgroup-uniform) an expert without a factor: the prior
+		if (tid < EX_TILE && tl.has(tid)) {
+			p.mu_e[tl.out(tid)] = 0.0;
+			p.var_e[tl.out(tid)] = p.kappa;
+		}
+		return;
+	}
+	const int n = (int)(hi - lo), NP = (n + 31) & ~31;
+	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;
+	experts_predict_body<false>(p, p.xs + lo * p.ldx, p.alpha + lo, p.factor + (int64_t)e * p.fslice, n, NP, tl, KT, nullptr, p.mu_e, p.var_e, As, Bs, ssq);
+}
+
+__global__ __launch_bounds__(256, 2)
+void experts_predict_routed_grad_kernel(ExpertsPredictGradArgs g, ExpertsRouteList r)
+{
+	__shared__ __attribute__((aligned(16))) double As[64 * LB_LDS];
+	__shared__ __attribute__((aligned(16))) double Bs[32 * LB_LDS];
+	__shared__ double ssq[4][EX_TILE];
+	__shared__ int64_t trow[EX_TILE], oidx[EX_TILE], gidx[EX_TILE];
+	const ExpertsPredictArgs& p = g.p;
+	const int tid = threadIdx.x;
+	const int e = r.wexp[blockIdx.x];
+	if (e < 0 || e >= r.E) return;          // (workgroup-uniform, before any barrier) a tile the list does not use
+	experts_routed_tile(r, p.M, p.ldm, g.ldg, g.lde, trow, oidx, gidx);
+	const ExpertsTileRouted tl{trow, oidx, gidx};
+	const int64_t lo = p.offsets[e], hi = p.offsets[e + 1];
+	if (!experts_has_factor(p, e, lo, hi)) {          // (workgroup-uniform) an expert without a factor: the prior, which is flat
+		if (tid < EX_TILE && tl.has(tid)) {
+			p.mu_e[tl.out(tid)] = 0.0;
+			p.var_e[tl.out(tid)] = p.kappa;
+		}
+		for (int i = tid; i < EX_TILE * p.d; i += 256) {
+			const int t = i / p.d, m = i - t * p.d;
+			if (tl.has(t)) {
+				g.gmu_e[tl.gout(t) + m] = 0.0;
+				g.gvar_e[tl.gout(t) + m] = 0.0;
+			}
+		}
+		return;
+	}
+	const int n = (int)(hi - lo), NP = (n + 31) & ~31;
+	const double* x = p.xs + lo * p.ldx;
+	const double* al = p.alpha + lo;
+	const double* V = p.factor + (int64_t)e * p.fslice;
+	double* KT = p.work + (int64_t)blockIdx.x * p.wslice;
+	double* VT = KT + (p.wslice >> 1);
+	experts_predict_body<true>(p, x, al, V, n, NP, tl, KT, VT, p.mu_e, p.var_e, As, Bs, ssq);
+	experts_grad_body(p, x, al, V, n, NP, tl, KT, VT, g.gmu_e, g.gvar_e, As, Bs);
+}
+
+// cent[e*ldc + m] = (sum over the expert's rows, in row order, of x_i[cols[m]] * inv_ls[m]) / n_e: one wave per expert, lane m owns coordinate m
+// and walks the rows one after the other.  An expert without rows (or whose offsets leave [0, N]) gets +inf in every coordinate.
+__global__ __launch_bounds__(64)
+void experts_centroids_kernel(const double* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const int32_t* offsets, const double* inv_ls,
+                              double* cent, int64_t ldc)
+{
+	const int64_t e = blockIdx.x;
+	const int64_t lo = offsets[e], hi = offsets[e + 1];
+	const bool ok = lo >= 0 && hi > lo && hi <= N;
+	for (int m = threadIdx.x; m < d; m += 64) {
+		double s = __builtin_huge_val();
+		if (ok) {
+			const int col = cols ? cols[m] : m;
+			const double il = inv_ls[m];
+			s = 0.0;
+			for (int64_t i = lo; i < hi; ++i) s += xs[i * ldx + col] * il;
+			s /= (double)(hi - lo);
+		}
+		cent[e * ldc + m] = s;
+	}
+}
+
+// (D, e) before (D', e'): the smaller distance, then the lower expert id
+__device__ __forceinline__ bool experts_nearer(double D, int e, double D2, int e2) { return D < D2 || (D == D2 && e < e2); }
+
+// The k nearest centroids of every test point: one wave per test point, lane l looks at the experts l, l + 64, ... in ascending order and keeps
+// its EX_ROUTE_K nearest as a sorted list in registers (every index below is a compile-time constant: no scratch); then k rounds in which the
+// wave agrees on the nearest list head (a butterfly minimum under a strict total order: the same answer in every lane) and its owner drops it;
+// lane r remembers the winner of round r, counts how many winners have a lower id, and stores its own at that rank: sel[t*k ..] ascending in
+// expert id.  D_e = sum_m (xt[cols[m]] inv_ls[m] - cent[e, m])^2, m ascending, capped at DBL_MAX (a NaN too), so that an expert without rows
+// (cent[e, 0] = +inf: D_e = +inf) comes after every other.  No barrier, no LDS, no atomics.
+__global__ __launch_bounds__(256)
+void experts_route_kernel(const double* cent, int64_t ldc, int64_t E, int d, const int32_t* cols, const double* inv_ls, const double* xt, int64_t M,
+                          int64_t ldt, int k, int32_t* sel)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (t >= M) return;          // (wave-uniform)
+	const double inf = __builtin_huge_val();
+	const double* x = xt + t * ldt;
+	double bd[EX_ROUTE_K];
+	int be[EX_ROUTE_K];
+#pragma unroll
+	for (int i = 0; i < EX_ROUTE_K; ++i) {
+		bd[i] = inf;
+		be[i] = INT32_MAX;
+	}
+	for (int64_t e64 = lane; e64 < E; e64 += 64) {
+		const int e = (int)e64;
+		const double* c = cent + e64 * ldc;
+		double D = 0.0;
+		for (int m = 0; m < d; ++m) {
+			const double u = x[cols ? cols[m] : m] * inv_ls[m] - c[m];
+			D = fma(u, u, D);
+		}
+		D = c[0] == inf ? inf : fmin(D, 1.7976931348623157e308);
+		if (experts_nearer(D, e, bd[EX_ROUTE_K - 1], be[EX_ROUTE_K - 1])) {
+#pragma unroll
+			for (int i = EX_ROUTE_K - 1; i >= 1; --i) {
+				const bool up = experts_nearer(D, e, bd[i - 1], be[i - 1]), here = experts_nearer(D, e, bd[i], be[i]);
+				bd[i] = up ? bd[i - 1] : (here ? D : bd[i]);
+				be[i] = up ? be[i - 1] : (here ? e : be[i]);
+			}
+			if (experts_nearer(D, e, bd[0], be[0])) {
+				bd[0] = D;
+				be[0] = e;
+			}
+		}
+	}
+	int mine = INT32_MAX;
+#pragma unroll
+	for (int r = 0; r < EX_ROUTE_K; ++r) {
+		if (r < k) {          // (uniform)
+			double hd = bd[0];
+			int he = be[0];
+#pragma unroll
+			for (int o = 32; o > 0; o >>= 1) {
+				const double od = __shfl_xor(hd, o);
+				const int oe = __shfl_xor(he, o);
+				if (experts_nearer(od, oe, hd, he)) {
+					hd = od;
+					he = oe;
+				}
+			}
+			if (be[0] == he) {
+#pragma unroll
+				for (int i = 0; i < EX_ROUTE_K - 1; ++i) {
+					bd[i] = bd[i + 1];
+					be[i] = be[i + 1];
+				}
+				bd[EX_ROUTE_K - 1] = inf;
+				be[EX_ROUTE_K - 1] = INT32_MAX;
+			}
+			if (lane == r) mine = he;
+		}
+	}
+	int rank = 0;
+#pragma unroll
+	for (int r = 0; r < EX_ROUTE_K; ++r)
+		if (r < k) rank += __shfl(mine, r) < mine ? 1 : 0;
+	if (lane < k && mine >= 0 && mine < E) sel[t * k + rank] = mine;
 }
 
 // One expert's term of the combination, the step both experts_combine_kernel and experts_combine_grad_kernel take (the same bits in mu and var):
@@ -626,6 +860,137 @@ int stpy_experts_combine_grad(int mode, int64_t E, int64_t M, int d, const void*
 	                         (double*)mu, (double*)var, (double*)dmu, (double*)dstd, ldo};
 	hipLaunchKernelGGL(experts_combine_grad_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
 	return check_launch("experts_combine_grad");
+}
+
+// ---- routing
+int64_t stpy_experts_route_max_k(void) { return EX_ROUTE_K; }
+
+int stpy_experts_centroids(int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const int32_t* offsets, int64_t E,
+                           const void* inv_ls, void* cent, int64_t ldc, void* stream)
+{
+	const char* who = "stpy_experts_centroids";
+	if (E == 0) return 0;
+	int rc;
+	if (experts_common_refused(who, STPY_K_SE, dtype, N, ldx, d, E, 0, &rc)) return rc;
+	if (ldc < d) { set_error("%s: leading dimension ldc=%lld (d=%d)", who, (long long)ldc, d); return -5; }
+	if ((N > 0 && !xs) || !offsets || !inv_ls || !cent) { set_error("%s: null pointer", who); return -3; }
+	if (((uintptr_t)xs | (uintptr_t)inv_ls | (uintptr_t)cent) & 7) { set_error("%s: arrays must be 8-byte aligned", who); return -21; }
+	hipLaunchKernelGGL(experts_centroids_kernel, dim3((unsigned)E), dim3(64), 0, (hipStream_t)stream, (const double*)xs, N, ldx, d, cols, offsets,
+	                   (const double*)inv_ls, (double*)cent, ldc);
+	return check_launch("experts_centroids");
+}
+
+// k outside [1, min(E, cap)] (-23), shared by the three entry points that take it
+static bool experts_k_refused(const char* who, int k, int64_t E, int64_t M, int* rc)
+{
+	*rc = 0;
+	if (k < 1 || k > EX_ROUTE_K || k > E) {
+		set_error("%s: k=%d outside [1, min(E=%lld, %d)] (stpy_experts_route_max_k)", who, k, (long long)E, EX_ROUTE_K);
+		*rc = -23;
+	} else if (M < 0 || M > INT32_MAX / k) { set_error("%s: M=%lld out of range (M k pair ids must stay below 2^31)", who, (long long)M); *rc = -9; }
+	return *rc != 0;
+}
+
+int stpy_experts_route(int dtype, const void* cent, int64_t ldc, int64_t E, int d, const int32_t* cols, const void* inv_ls,
+                       const void* xt, int64_t M, int64_t ldt, int k, int32_t* sel, void* stream)
+{
+	const char* who = "stpy_experts_route";
+	if (E == 0 || M == 0) return 0;
+	int rc;
+	if (experts_common_refused(who, STPY_K_SE, dtype, 0, d, d, E, 0, &rc)) return rc;
+	if (experts_k_refused(who, k, E, M, &rc)) return rc;
+	if (ldc < d || ldt < d) { set_error("%s: leading dimensions ldc=%lld ldt=%lld (d=%d)", who, (long long)ldc, (long long)ldt, d); return -5; }
+	if (!cent || !inv_ls || !xt || !sel) { set_error("%s: null pointer", who); return -3; }
+	if ((((uintptr_t)cent | (uintptr_t)inv_ls | (uintptr_t)xt) & 7) || ((uintptr_t)sel & 3)) { set_error("%s: cent / inv_ls / xt must be 8-byte aligned, sel 4-byte", who); return -21; }
+	hipLaunchKernelGGL(experts_route_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const double*)cent, ldc, E, d, cols,
+	                   (const double*)inv_ls, (const double*)xt, M, ldt, k, sel);
+	return check_launch("experts_route");
+}
+
+int64_t stpy_experts_predict_routed_workspace_bytes(int dtype, int64_t nmax, int d, int64_t T)
+{
+	(void)d;
+	if (dtype != STPY_F64 || nmax <= 0 || nmax > LB_MAX_N || T <= 0) return 0;
+	return T * experts_predict_slice(nmax) * (int64_t)sizeof(double);
+}
+
+int64_t stpy_experts_predict_routed_grad_workspace_bytes(int dtype, int64_t nmax, int d, int64_t T)
+{
+	return 2 * stpy_experts_predict_routed_workspace_bytes(dtype, nmax, d, T);
+}
+
+// the checks the two routed predictions share (gmu_s == NULL: without gradients)
+static int experts_routed_refused(const char* who, bool grad, int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* offsets,
+                                  int64_t E, int64_t nmax, const void* inv_ls, double kappa, const void* factor, int64_t factor_bytes, const void* alpha,
+                                  const int32_t* info, const void* xt, int64_t M, int64_t ldt, int k, const int32_t* wexp, const int32_t* wpair, int64_t T,
+                                  const void* mu_s, const void* var_s, int64_t ldm, const void* gmu_s, const void* gvar_s, int64_t ldg, int64_t lde,
+                                  const void* work, int64_t work_bytes)
+{
+	int rc;
+	if (experts_common_refused(who, kind, dtype, N, ldx, d, E, nmax, &rc)) return rc;
+	if (experts_k_refused(who, k, E, M, &rc)) return rc;
+	if (T < 0 || T > INT32_MAX) { set_error("%s: T=%lld tiles out of range", who, (long long)T); return -9; }
+	if (ldt < d || ldm < M) { set_error("%s: leading dimensions ldt=%lld (d=%d) ldm=%lld (M=%lld)", who, (long long)ldt, d, (long long)ldm, (long long)M); return ldt < d ? -5 : -13; }
+	if (grad && (ldg < d || lde / ldg < M)) {
+		set_error("%s: gradient strides ldg=%lld (d=%d) lde=%lld (at least M ldg, M=%lld)", who, (long long)ldg, d, (long long)lde, (long long)M);
+		return -19;
+	}
+	if (!xs || !offsets || !inv_ls || !factor || !alpha || !info || !xt || !wexp || !wpair || !mu_s || !var_s || !work || (grad && (!gmu_s || !gvar_s))) {
+		set_error("%s: null pointer", who);
+		return -3;
+	}
+	if (!(kappa > 0.0) || !is_finite(kappa)) { set_error("%s: kappa=%g must be positive and finite", who, kappa); return -11; }
+	const int64_t need = (grad ? 2 : 1) * stpy_experts_predict_routed_workspace_bytes(dtype, nmax, d, T), fneed = stpy_experts_factor_bytes(dtype, nmax, E);
+	if (work_bytes < need) {
+		set_error("%s: workspace of %lld bytes, %lld needed (see the *_workspace_bytes query for these arguments)", who, (long long)work_bytes, (long long)need);
+		return -20;
+	}
+	if (factor_bytes < fneed) {
+		set_error("%s: factor buffer of %lld bytes, %lld needed (stpy_experts_factor_bytes)", who, (long long)factor_bytes, (long long)fneed);
+		return -22;
+	}
+	if ((((uintptr_t)xs | (uintptr_t)xt | (uintptr_t)alpha | (uintptr_t)mu_s | (uintptr_t)var_s | (uintptr_t)gmu_s | (uintptr_t)gvar_s) & 7)
+	    || (((uintptr_t)work | (uintptr_t)factor) & 15) || (((uintptr_t)wexp | (uintptr_t)wpair) & 3)) {
+		set_error("%s: work and factor must be 16-byte aligned, the other arrays 8-byte, wexp / wpair 4-byte", who);
+		return -21;
+	}
+	return 0;
+}
+
+int stpy_experts_predict_routed(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const int32_t* offsets,
+                                int64_t E, int64_t nmax, const void* inv_ls, double kappa, const void* factor, int64_t factor_bytes,
+                                const void* alpha, const int32_t* info, const void* xt, int64_t M, int64_t ldt,
+                                int k, const int32_t* wexp, const int32_t* wpair, int64_t T,
+                                void* mu_s, void* var_s, int64_t ldm, void* work, int64_t work_bytes, void* stream)
+{
+	if (E == 0 || N == 0 || M == 0 || T == 0) return 0;
+	const int rc = experts_routed_refused("stpy_experts_predict_routed", false, kind, dtype, xs, N, ldx, d, offsets, E, nmax, inv_ls, kappa, factor, factor_bytes,
+	                                      alpha, info, xt, M, ldt, k, wexp, wpair, T, mu_s, var_s, ldm, nullptr, nullptr, 0, 0, work, work_bytes);
+	if (rc) return rc;
+	ExpertsPredictArgs p{(const double*)xs, N, ldx, d, cols, offsets, (int)nmax, (const double*)inv_ls, kappa, (const double*)factor, experts_factor_slice(nmax),
+	                     (const double*)alpha, info, (const double*)xt, M, ldt, (double*)mu_s, (double*)var_s, ldm, (double*)work, experts_predict_slice(nmax),
+	                     0, kind};
+	hipLaunchKernelGGL(experts_predict_routed_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, p, ExpertsRouteList{wexp, wpair, k, E});
+	return check_launch("experts_predict_routed");
+}
+
+int stpy_experts_predict_routed_grad(int kind, int dtype, const void* xs, int64_t N, int64_t ldx, int d, const int32_t* cols, const int32_t* offsets,
+                                     int64_t E, int64_t nmax, const void* inv_ls, double kappa, const void* factor, int64_t factor_bytes,
+                                     const void* alpha, const int32_t* info, const void* xt, int64_t M, int64_t ldt,
+                                     int k, const int32_t* wexp, const int32_t* wpair, int64_t T,
+                                     void* mu_s, void* var_s, int64_t ldm, void* gmu_s, void* gvar_s, int64_t ldg, int64_t lde,
+                                     void* work, int64_t work_bytes, void* stream)
+{
+	if (E == 0 || N == 0 || M == 0 || T == 0) return 0;
+	const int rc = experts_routed_refused("stpy_experts_predict_routed_grad", true, kind, dtype, xs, N, ldx, d, offsets, E, nmax, inv_ls, kappa, factor,
+	                                      factor_bytes, alpha, info, xt, M, ldt, k, wexp, wpair, T, mu_s, var_s, ldm, gmu_s, gvar_s, ldg, lde, work, work_bytes);
+	if (rc) return rc;
+	ExpertsPredictGradArgs g{{(const double*)xs, N, ldx, d, cols, offsets, (int)nmax, (const double*)inv_ls, kappa, (const double*)factor, experts_factor_slice(nmax),
+	                          (const double*)alpha, info, (const double*)xt, M, ldt, (double*)mu_s, (double*)var_s, ldm, (double*)work, 2 * experts_predict_slice(nmax),
+	                          0, kind},
+	                         (double*)gmu_s, (double*)gvar_s, ldg, lde};
+	hipLaunchKernelGGL(experts_predict_routed_grad_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, g, ExpertsRouteList{wexp, wpair, k, E});
+	return check_launch("experts_predict_routed_grad");
 }
 
 }  // extern "C"
